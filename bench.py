@@ -14,7 +14,14 @@ Scaling: the job is FIXED (64 objects) and LPT-sharded across the N ranks
 config 4 (64 objects x 4096 points, 8 per GPU at N=8).
 
 Inputs are resident in HBM before the timed region (dsr_batch_create); each step
-re-initialises the optimizer state on device and runs all iterations.  At N=1 rank 0
+re-initialises the optimizer state on device and runs all iterations.
+
+A plain run does only what the headline figure needs: set-up, ``--warmup`` steps, the
+``--steps`` timed steps, the ``--dump-outputs`` arrays if asked for, and the result line
+(with the kernel statistics the timed steps themselves recorded).  Every other leg below
+runs only with ``--full`` (and then unless its ``--no-*`` switch is given).
+
+With ``--full`` at N=1 rank 0
 also reports: the exact-decode leg (``value_exact``: DSR_LITE=0, every ray sample
 decoded in 3xFP16), the fp32-arithmetic leg (``fp32_leg``: the exact pass and the Jacobian
 on the fp32-MFMA kernels, their rates against the 157.3 TF fp32 MFMA peak), the three MFMA
@@ -23,10 +30,19 @@ Redwood keyframe leg (BASELINE config 5, ``keyframe``), one 16-object KITTI fram
 (config 3 of the list, ``config2_frame``) and one object per ``reconstruct_object`` call
 (``config1_single``).
 
-Every N also runs a ``config4`` leg: BASELINE config 4 (64 objects x 4096 points, the same
-LPT sharding, 8 per GPU at N=8), so one N=1,2,4,8 sweep gives both strong-scaling curves.
+With ``--full`` every N also runs a ``config4`` leg: BASELINE config 4 (64 objects x 4096
+points, the same LPT sharding, 8 per GPU at N=8), so one N=1,2,4,8 sweep gives both
+strong-scaling curves, and re-creates the job's batch from the context's warm pool
+(``host_inclusive_value``).
 
-Usage: python bench.py [--gpus N --steps K --warmup W --objects B --pts P --weak]
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last timed step returned
+to its caller — every object's record, in input order — as float32 ``DIR/<name>.npy``:
+``loss`` (n), ``is_good`` (n), ``iters_done`` (n), ``t_cam_obj`` (n, 4, 4), ``code`` (n, 64);
+pose and code of an object that did not converge are NaN.  The inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
+
+Usage: python bench.py [--gpus N --steps K --warmup W --objects B --pts P --weak --full
+                        --dump-outputs DIR]
        N>1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) the ranks are
        the launcher's; without it bench.py starts ``torch.distributed.run --nproc-per-node N``
        itself as a child process (before any GPU call) and exits with its status.
@@ -378,6 +394,25 @@ def record_rows(res):
                         if r["is_good"] else [np.nan] * 80) for r in res], np.float32)
 
 
+def dump_outputs(dirname, res, code_len=64):
+    """--dump-outputs: the last timed step's results (what ``ResidentShard.run`` handed its
+    caller, in input order) as float32 arrays, one .npy per field."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(res)
+    pose = np.full((n, 4, 4), np.nan, np.float32)
+    code = np.full((n, code_len), np.nan, np.float32)
+    for i, r in enumerate(res):
+        if r["is_good"]:
+            pose[i] = np.asarray(r["t_cam_obj"], np.float32).reshape(4, 4)
+            code[i] = np.asarray(r["code"], np.float32).reshape(-1)
+    arrays = {"loss": np.array([r["loss"] for r in res], np.float32),
+              "is_good": np.array([float(r["is_good"]) for r in res], np.float32),
+              "iters_done": np.array([r["iters_done"] for r in res], np.float32),
+              "t_cam_obj": pose, "code": code}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def config4_leg(opt, rank, coll_dev, barrier, dist, torch, steps=3, n_obj=64, n_pts=4096, dump=""):
     """BASELINE config 4: ONE job of 64 synthetic KITTI objects x 4096 points, LPT-sharded over
     the ranks (8 per GPU at N=8) with the record gather; same timing rules as the main line."""
@@ -457,15 +492,29 @@ def parse_args():
     ap.add_argument("--objects", type=int, default=64, help="objects in the job (per GPU with --weak)")
     ap.add_argument("--pts", type=int, default=2048, help="surface points per object (config 4: 4096)")
     ap.add_argument("--weak", action="store_true", help="every rank its own --objects objects")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the exact-decode and keyframe legs")
-    ap.add_argument("--no-config4", action="store_true", help="skip the 64 x 4096-point config-4 leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: CPU baseline, exact-decode, fp32, "
+                         "one-stream, keyframe and small-batch legs, the bare-MFMA rate, the warm batch "
+                         "creation and the config-4 leg (each unless its --no-* switch is given)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's results as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the exact-decode, fp32, one-stream, keyframe and small-batch legs")
+    ap.add_argument("--no-config4", action="store_true",
+                    help="with --full: skip the 64 x 4096-point config-4 leg")
     ap.add_argument("--dump-records", default="", help="rank 0 writes the last step's gathered records (.npy; "
                                                        "the config-4 leg's to <name>_c4.npy)")
     ap.add_argument("--c4-objects", type=int, default=64, help="config-4 leg: objects (rehearsals only)")
     ap.add_argument("--c4-pts", type=int, default=4096, help="config-4 leg: points per object (rehearsals only)")
     gpus_given = any(a == "--gpus" or a.startswith("--gpus=") for a in sys.argv[1:])
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # a plain run is the headline figure alone; every other leg needs --full
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.extra = args.full and not args.no_extra
+    args.config4 = args.full and not args.no_config4 and not args.weak
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -577,9 +626,11 @@ def main():
                      distinct_devices=len({(d["host"], d["pci_bus_id"], d["pci_domain_id"]) for d in devs}))
     if args.dump_records and rank == 0 and res is not None:
         np.save(args.dump_records, record_rows(res))
+    if args.dump_outputs and rank == 0 and res is not None:
+        dump_outputs(args.dump_outputs, res, opt.code_len)
     value = n_job * args.steps / elapsed
     roof = kernel_rooflines(acc) if acc else {}
-    loop = measured_mfma_loop(local) if rank == 0 and acc and not args.no_extra else None
+    loop = measured_mfma_loop(local) if rank == 0 and acc and args.extra else None
     if loop:
         for name, e in roof.items():     # the split kernels' fp32-equivalent rate is 1/3 of fp16
             k = 1.0 if "lite" in name else 1.0 / SPLIT_PRODUCTS
@@ -649,7 +700,7 @@ def main():
             "device_ms_per_step": round(acc["total_ms"] / stats_steps, 3) if acc else None,
             "stats_steps": stats_steps,
             "good_fraction": n_good / float(n_job * args.steps),
-            # inputs handed over in host memory: the upload added to one step (set below from a
+            # inputs handed over in host memory: the upload added to one step (with --full set below from a
             # batch created against the context's warm pool — the steady state of a stream of jobs;
             # the first creation in a process also pays its hipMallocs / event creation)
             "host_inclusive_value": None,
@@ -662,20 +713,21 @@ def main():
             out["roofline"]["traffic"] = tr[0]
             out["roofline"]["traffic_source"] = tr[1]
     shard.close()
-    t0 = time.perf_counter()
-    warm = ResidentShard(opt, objs, device=coll_dev)   # the same job again, from the pooled blocks
-    create_warm_s = time.perf_counter() - t0
-    warm.close()
-    if rank == 0:
-        out["batch_create_ms"] = create_warm_s * 1e3
-        out["host_inclusive_value"] = n_job / (elapsed / args.steps + create_warm_s)
-    if not args.no_config4 and not args.weak:
+    if args.full:
+        t0 = time.perf_counter()
+        warm = ResidentShard(opt, objs, device=coll_dev)   # the same job again, from the pooled blocks
+        create_warm_s = time.perf_counter() - t0
+        warm.close()
+        if rank == 0:
+            out["batch_create_ms"] = create_warm_s * 1e3
+            out["host_inclusive_value"] = n_job / (elapsed / args.steps + create_warm_s)
+    if args.config4:
         c4 = config4_leg(opt, rank, coll_dev, barrier, dist, torch, steps=min(args.steps, 3), n_obj=args.c4_objects,
                          n_pts=args.c4_pts,
                          dump=args.dump_records[:-4] + "_c4.npy" if args.dump_records.endswith(".npy") else "")
         if rank == 0:
             out["config4"] = c4
-    if world == 1 and not args.no_extra:
+    if world == 1 and args.extra:
         # exact-decode leg: DSR_LITE=0 (every in-ball sample decoded in 3xFP16), same job
         k = min(args.steps, 3)
         with env_set(DSR_LITE="0"):
@@ -733,7 +785,7 @@ def main():
         out["keyframe"] = keyframe_leg(dec)
         out.update(small_legs(opt, objs))
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n_pts=args.pts)
         print(json.dumps(out), flush=True)
     if dist is not None:

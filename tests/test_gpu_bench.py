@@ -56,6 +56,40 @@ def test_bench_two_ranks_gather_equals_one_process(tmp_path, n):
 
 
 @pytest.mark.timeout(300)
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain ``bench.py --gpus 1 --steps K --warmup W`` runs no leg beside the timed steps (those
+    need ``--full``), reports ``ms_per_step`` for exactly K steps, and ``--dump-outputs DIR`` writes
+    the last timed step's results as float32 arrays: the same numbers as ``--dump-records``."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    d = tmp_path / "out"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--objects", "8",
+           "--dump-outputs", str(d), "--dump-records", str(tmp_path / "rec.npy")]
+    p = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["unit"] == "object-reconstructions/sec" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and "fp16" in out["dtype"]
+    assert np.isclose(out["value"], 8 / (out["ms_per_step"] * 1e-3), rtol=1e-9)
+    assert out["rooflines"] and out["stats_steps"] == 2          # read from the timed steps themselves
+    for leg in ("config4", "value_exact", "fp32_leg", "rooflines_one_stream", "keyframe", "config2_frame",
+                "config1_single", "batch_create_ms"):
+        assert leg not in out, leg
+    assert out["cpu_baseline"] is None and out["mfma_loop"] is None and out["host_inclusive_value"] is None
+    rec = np.load(tmp_path / "rec.npy")
+    assert sorted(f.name for f in d.iterdir()) == ["code.npy", "is_good.npy", "iters_done.npy", "loss.npy",
+                                                   "t_cam_obj.npy"]
+    got = {f.stem: np.load(f) for f in d.iterdir()}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["t_cam_obj"].shape == (8, 4, 4) and got["code"].shape == (8, 64)
+    assert (got["is_good"] == 1).all()
+    flat = np.concatenate([got["loss"][:, None], got["is_good"][:, None], got["iters_done"][:, None],
+                           got["t_cam_obj"].reshape(8, 16), got["code"]], 1)
+    assert np.array_equal(flat.view(np.uint32), rec.view(np.uint32))
+
+
+@pytest.mark.timeout(300)
 def test_bench_rccl_path_on_one_rank(tmp_path):
     """The driver's N>1 runs go through torch.distributed.run with backend "nccl" (RCCL over
     xGMI), which needs one GPU per rank.  On this one-GPU box the same code path runs with one
@@ -87,7 +121,7 @@ def test_bench_eight_ranks_rehearse_the_driver_command(tmp_path):
     points here, 8 per rank as at N = 8), one all-gather returns every record to rank 0 — and
     both record sets are bitwise those of ``--gpus 1``."""
     extra = ["--objects", "16", "--c4-objects", "64", "--c4-pts", "1024"]
-    args8 = [a for a in ARGS if a not in ("--no-config4",)]
+    args8 = ["--full"] + [a for a in ARGS if a not in ("--no-config4",)]    # the config-4 leg is a --full leg
 
     def run(n, dump):
         env = dict(os.environ, DSR_BENCH_BACKEND="gloo")

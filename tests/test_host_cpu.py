@@ -83,7 +83,63 @@ def test_short_code_is_rejected_before_c():
         mex.extract_mesh_from_code(short)
 
 
-REF_RECONSTRUCT = "/root/reference/reconstruct"
+# Stand-ins for the ingest modules a DSP-SLAM checkout provides (written for this test, held in no
+# other tree): they take from this package exactly the names the originals take (see the test's
+# docstring) and construct the two sequence classes get_sequence dispatches to.
+_STANDIN_HEAD = """\
+import os
+import numpy as np
+import cv2
+from reconstruct.loss_utils import get_rays, get_time
+from reconstruct.utils import ForceKeyErrorDict, read_calib_file, load_velo_scan
+from reconstruct import get_detectors
+"""
+_STANDIN_INGEST = {
+    "kitti_sequence": _STANDIN_HEAD + """
+
+class KITIISequence:
+    def __init__(self, data_dir, configs):
+        self.configs = configs
+        self.num_frames = len(os.listdir(os.path.join(data_dir, "image_2")))
+        calib = read_calib_file(os.path.join(data_dir, "calib.txt"))
+        proj = calib["P2"].reshape(3, 4)
+        self.K_cam = proj[:, :3].astype(np.float32)
+        self.invK_cam = np.linalg.inv(self.K_cam).astype(np.float32)
+        cam2_from_cam0 = np.eye(4)
+        cam2_from_cam0[0, 3] = proj[0, 3] / proj[0, 0]
+        cam0_from_velo = np.vstack([calib["Tr"].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]])
+        self.T_cam_velo = (cam2_from_cam0 @ cam0_from_velo).astype(np.float32)
+        self.detector_2d, self.detector_3d = get_detectors(configs)
+""",
+    "mono_sequence": _STANDIN_HEAD + """
+
+class MonoSequence:
+    def __init__(self, data_dir, configs):
+        self.configs = configs
+        fs = cv2.FileStorage(configs.slam_config_path, cv2.FILE_STORAGE_READ)
+        fx, fy, cx, cy, self.k1, self.k2 = (fs.getNode("Camera." + k).real()
+                                            for k in ("fx", "fy", "cx", "cy", "k1", "k2"))
+        self.K_cam = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+        self.invK_cam = np.linalg.inv(self.K_cam)
+        self.detector_2d = get_detectors(configs)
+""",
+    # present in the directory, never loaded: only the four named ingest modules resolve there
+    "loss": "raise RuntimeError('reconstruct.loss must never resolve outside the package')\n",
+}
+
+
+@pytest.fixture
+def ingest_dir(tmp_path):
+    """The directory ``DSR_REFERENCE_RECONSTRUCT`` names: the caller's own (a DSP-SLAM checkout's
+    ``reconstruct/``) when the variable is set and provides the modules, else the stand-ins."""
+    own = os.environ.get("DSR_REFERENCE_RECONSTRUCT", "")
+    if own and all(os.path.isfile(os.path.join(own, n + ".py")) for n in ("kitti_sequence", "mono_sequence")):
+        return own
+    d = tmp_path / "ingest"
+    d.mkdir()
+    for name, text in _STANDIN_INGEST.items():
+        (d / (name + ".py")).write_text(text)
+    return str(d)
 
 
 class _CV2Stub:
@@ -104,10 +160,11 @@ class _CV2Stub:
             return type("Node", (), {"real": lambda self: v})()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_RECONSTRUCT), reason="reference tree not present (GPU box)")
-def test_ingest_hook_runs_the_reference_modules(tmp_path, monkeypatch):
+def test_ingest_hook_runs_the_reference_modules(tmp_path, monkeypatch, ingest_dir):
     """System.cc:99 calls reconstruct.get_sequence at every start-up.  Through the ingest hook
-    the build loads the reference's OWN kitti_sequence.py / mono_sequence.py, which import
+    the build loads kitti_sequence.py / mono_sequence.py from the directory
+    DSR_REFERENCE_RECONSTRUCT names (the reference's own when the caller's environment points
+    there, else stand-ins with the same imports), which import
     get_rays / get_time from reconstruct.loss_utils and read_calib_file / load_velo_scan /
     ForceKeyErrorDict from reconstruct.utils (kitti_sequence.py:22-24, mono_sequence.py:22-24):
     both sequences construct, calibration parsed by this package's reader.  Nothing else
@@ -124,7 +181,8 @@ def test_ingest_hook_runs_the_reference_modules(tmp_path, monkeypatch):
         if not k.startswith("__"):
             setattr(cv2, k, v)
     monkeypatch.setitem(sys.modules, "cv2", cv2)
-    monkeypatch.setenv("DSR_REFERENCE_RECONSTRUCT", REF_RECONSTRUCT)
+    monkeypatch.setenv("DSR_REFERENCE_RECONSTRUCT", ingest_dir)
+    assert os.path.isfile(os.path.join(ingest_dir, "loss.py"))
     for name in ("kitti_sequence", "mono_sequence"):
         monkeypatch.delitem(sys.modules, "reconstruct." + name, raising=False)
     # a KITTI sequence directory: calib.txt (P2 with a baseline term, Tr), two images, a scan

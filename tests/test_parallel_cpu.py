@@ -272,6 +272,41 @@ def test_bench_spawns_its_own_ranks(monkeypatch):
     assert args.gpus == 2 == world
 
 
+def test_bench_legs_need_full(monkeypatch, tmp_path):
+    """A plain bench run times its steps and nothing else: every other leg is behind ``--full``,
+    where the ``--no-*`` switches still take single legs out.  ``--dump-outputs`` writes one
+    float32 array per result field, NaN pose and code for an object that did not converge."""
+    import sys
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+
+    def legs(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        a, _ = bench.parse_args()
+        return a.cpu_baseline, a.extra, a.config4
+
+    assert legs("--gpus", "1", "--steps", "3", "--warmup", "1") == (False, False, False)
+    assert legs("--no-extra", "--no-cpu-baseline", "--no-config4") == (False, False, False)
+    assert legs("--full") == (True, True, True)
+    assert legs("--full", "--no-extra", "--no-cpu-baseline") == (False, False, True)
+    assert legs("--full", "--weak") == (True, True, False)
+    with pytest.raises(SystemExit):
+        legs("--steps", "0")
+    res = [dict(loss=0.5, is_good=True, iters_done=10, t_cam_obj=np.eye(4), code=np.arange(64.0)),
+           dict(loss=2.0, is_good=False, iters_done=3, t_cam_obj=None, code=None)]
+    bench.dump_outputs(str(tmp_path / "o"), res)
+    got = {f[:-4]: np.load(tmp_path / "o" / f) for f in os.listdir(tmp_path / "o")}
+    assert sorted(got) == ["code", "is_good", "iters_done", "loss", "t_cam_obj"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].tolist() == [0.5, 2.0] and got["is_good"].tolist() == [1.0, 0.0]
+    assert got["iters_done"].tolist() == [10.0, 3.0]
+    assert np.array_equal(got["t_cam_obj"][0], np.eye(4)) and np.isnan(got["t_cam_obj"][1]).all()
+    assert np.array_equal(got["code"][0], np.arange(64)) and np.isnan(got["code"][1]).all()
+
+
 def test_lpt_partition_balances_and_covers():
     from reconstruct.parallel import lpt_partition
 

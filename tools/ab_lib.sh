@@ -10,14 +10,14 @@ python tools/batch_sig.py --compare gpurun_out/${TAG}_sigA.npz gpurun_out/${TAG}
 for rep in 1 2; do
   for v in A B; do
     lib=$A; [ $v = B ] && lib=$B
-    DSR_LIB=$lib timeout -k 10 200 python bench.py --steps ${STEPS:-5} --warmup 1 --no-extra --no-cpu-baseline ${BENCH_ARGS:-} \
+    DSR_LIB=$lib timeout -k 10 200 python bench.py --full --steps ${STEPS:-5} --warmup 1 --no-extra --no-cpu-baseline ${BENCH_ARGS:-} \
       > gpurun_out/${TAG}_${v}${rep}.json 2> gpurun_out/${TAG}_${v}${rep}.err
     rc=$?; echo "$v$rep rc=$rc"; [ $rc -eq 0 ] || exit $rc
   done
 done
 for v in A B; do
   lib=$A; [ $v = B ] && lib=$B
-  DSR_LIB=$lib DSR_LITE=0 DSR_STREAMS=1 timeout -k 10 200 python bench.py --steps 3 --warmup 1 --no-extra --no-cpu-baseline \
+  DSR_LIB=$lib DSR_LITE=0 DSR_STREAMS=1 timeout -k 10 200 python bench.py --full --steps 3 --warmup 1 --no-extra --no-cpu-baseline \
     > gpurun_out/${TAG}_${v}x.json 2> gpurun_out/${TAG}_${v}x.err
   rc=$?; echo "${v}x rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done

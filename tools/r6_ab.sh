@@ -8,6 +8,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 200 --timeout-me
 rc=$?; echo "tests rc=$rc"; [ $rc -le 1 ] || exit $rc
 for r in 1 2; do
   for lib in libdsr.so $X; do
-    DSR_LIB=$L/$lib timeout -k 10 400 python bench.py --steps 10 --warmup 2 > gpurun_out/${T}_${lib%.so}_$r.json 2> gpurun_out/${T}_${lib%.so}_$r.err || exit $?
+    O=${OUT:-bench_out}; mkdir -p $O
+    DSR_LIB=$L/$lib timeout -k 10 400 python bench.py --full --steps 10 --warmup 2 > $O/${T}_${lib%.so}_$r.json 2> $O/${T}_${lib%.so}_$r.err || exit $?
   done
 done
