@@ -22,6 +22,7 @@
 #include "../../include/dsr.h"
 #include "dsr_kernels.hpp"
 #include "dsr_mc.hpp"
+#include "dsr_mesh.hpp"
 
 #ifndef DSR_DEFAULT_FWD_VARIANT
 #define DSR_DEFAULT_FWD_VARIANT 12  // split-fp16 (3xFP16) + s_setprio (A/B: tools/fwd_variants.py)
@@ -2383,6 +2384,9 @@ int dsr_decoder_info_get(const dsr_decoder* dec, dsr_decoder_info* info) {
 // ------------------------------------------------------------------------------------
 // mesh extraction (MeshExtractor, optimizer.py:216-233; utils.py:119-140)
 // ------------------------------------------------------------------------------------
+struct MeshBatch;
+static void mesh_batch_free(MeshBatch* b);
+
 struct dsr_mesher {
   dsr_ctx* ctx = nullptr;
   const dsr_decoder* dec = nullptr;
@@ -2396,11 +2400,14 @@ struct dsr_mesher {
   int *flag = nullptr, *vidx = nullptr, *ntri = nullptr, *toff = nullptr, *bsum = nullptr, *tot = nullptr;
   float* verts = nullptr;
   int* faces = nullptr;
+  MeshBatch* mb = nullptr;     // dsr_mesher_run_batch's slots (allocated on its first call)
+  dsr_mesher_stats st{};       // its last call
 };
 
 int dsr_mesher_destroy(dsr_mesher* m) {
   if (!m) return 0;
   hipSetDevice(m->ctx->device);
+  mesh_batch_free(m->mb);
   for (void* p : m->allocs) hipFree(p);
   delete m;
   return 0;
@@ -2552,6 +2559,351 @@ int dsr_mc_volume(dsr_ctx* ctx, const float* vol, int vol_dim, float level, floa
   if (!mesher_alloc_mc(&m)) return fail(ctx, "hipMalloc failed (marching cubes)");
   DSR_CHECK(ctx, hipMemcpyAsync(m.vol, vol, sizeof(float) * (size_t)m.n, hipMemcpyHostToDevice, ctx->stream));
   return mc_run(&m, level, verts, vcap, faces, fcap, n_verts, n_faces);
+}
+
+// ------------------------------------------------------------------------------------
+// batched mesh extraction (dsr_mesh.hpp)
+// ------------------------------------------------------------------------------------
+// S slots of everything a mesh needs; a call runs its codes in passes of up to S.  S grows with
+// the calls' code counts up to MESH_MAX_SLOTS and while one pass's buffers stay within
+// MESH_BUDGET (the marching-cubes buffers hold the worst case of every slot: ~270 MB per slot at
+// 128^3, so 6 slots there; 16 up to 96^3).
+static constexpr int MESH_MAX_SLOTS = 16;
+static constexpr size_t MESH_BUDGET = (size_t)2 << 30;
+static constexpr float MESH_MARGIN = 0.01f;      // §3.4's first-iteration margin
+
+struct MeshBatch {
+  int S = 0, np = 0, ntl = 0, n_rb = 0;
+  int last_ns = 0;             // slots of the last pass (dsr_mesher_peek)
+  bool last_sign = false;
+  std::vector<void*> allocs;
+  float4* pts = nullptr;       // the grid, once per slot (the kernels index it by ObjDesc.cand_off)
+  float *lite = nullptr, *vol = nullptr, *codes = nullptr, *b0 = nullptr, *b4 = nullptr, *verts = nullptr;
+  unsigned char *refine = nullptr, *tflag = nullptr;
+  int *flag = nullptr, *vidx = nullptr, *ntri = nullptr, *toff = nullptr, *bsum = nullptr, *faces = nullptr;
+  int *tmark = nullptr, *tpos = nullptr;
+  Tile *ltiles = nullptr, *atiles = nullptr, *etiles = nullptr, *rtiles = nullptr;
+  ObjDesc* desc = nullptr;
+  ObjState* st = nullptr;
+  // one record of ints read back per pass: vertex offsets (S+1), face offsets (S+1), counters
+  // (MS_INTS), tile counts (4: lite, all, band, redo), per-slot error bits / violations / redo
+  // flag (S each), the lite kernel's wait record (STD_INTS)
+  int* rb = nullptr;
+  int *offs_v = nullptr, *offs_f = nullptr, *stat = nullptr, *cnt = nullptr, *slot_err = nullptr,
+      *slot_viol = nullptr, *slot_redo = nullptr, *diag = nullptr;
+  hipEvent_t ev[4] = {};
+  std::vector<float> hcodes, hv;
+  std::vector<int> hrb, hf;
+};
+
+static void mesh_batch_free(MeshBatch* b) {
+  if (!b) return;
+  for (void* p : b->allocs) hipFree(p);
+  for (hipEvent_t e : b->ev)
+    if (e) hipEventDestroy(e);
+  delete b;
+}
+
+static size_t mesh_slot_bytes(const dsr_mesher* m) {
+  const size_t n = m->n, nc = (size_t)(m->d - 1) * (m->d - 1) * (m->d - 1), np = (n + LTILE - 1) / LTILE * LTILE;
+  return np * (sizeof(float4) + 2 * sizeof(float) + 1) + sizeof(int) * std::max(3 * n, np) + sizeof(int) * 3 * n +
+         2 * sizeof(int) * nc + sizeof(float) * 9 * n + sizeof(int) * 3 * DSR_MC_MAX_TRI * nc +
+         (size_t)m->nt * (3 * sizeof(Tile) + 2 * sizeof(int) + 1) + np / LTILE * sizeof(Tile);
+}
+
+// (re)allocate the batch half of a mesher for S slots; false: out of memory (nothing is kept)
+static bool mesh_batch_alloc(dsr_mesher* m, int S) {
+  mesh_batch_free(m->mb);
+  m->mb = nullptr;
+  auto* b = new MeshBatch();
+  const int n = m->n, nt = m->nt, d = m->d, nc = (d - 1) * (d - 1) * (d - 1);
+  const int np = (n + LTILE - 1) / LTILE * LTILE, ntl = np / LTILE;
+  const size_t Sz = (size_t)S, fl = std::max((size_t)3 * n, (size_t)np);
+  b->S = S;
+  b->np = np;
+  b->ntl = ntl;
+  b->n_rb = 2 * (S + 1) + MS_INTS + 4 + 3 * S + STD_INTS;
+  const size_t nb = (Sz * std::max(fl, (size_t)std::max(nc, nt)) + MC_SCAN_BLOCK - 1) / MC_SCAN_BLOCK;
+  bool ok = true;
+  auto A = [&](void** p, size_t bytes) {
+    if (!ok) return;
+    if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) {
+      (void)hipGetLastError();
+      ok = false;
+      return;
+    }
+    b->allocs.push_back(*p);
+  };
+  A((void**)&b->pts, sizeof(float4) * Sz * np);
+  A((void**)&b->lite, sizeof(float) * Sz * np);
+  A((void**)&b->vol, sizeof(float) * Sz * np);
+  A((void**)&b->refine, Sz * np);
+  A((void**)&b->codes, sizeof(float) * Sz * CODE);
+  A((void**)&b->b0, sizeof(float) * Sz * HID);
+  A((void**)&b->b4, sizeof(float) * Sz * HID);
+  A((void**)&b->flag, sizeof(int) * Sz * fl);          // (the lite kernel's dead flags live here too)
+  A((void**)&b->vidx, sizeof(int) * Sz * 3 * n);
+  A((void**)&b->ntri, sizeof(int) * Sz * nc);
+  A((void**)&b->toff, sizeof(int) * Sz * nc);
+  A((void**)&b->bsum, sizeof(int) * nb);
+  A((void**)&b->verts, sizeof(float) * 3 * Sz * 3 * n);
+  A((void**)&b->faces, sizeof(int) * 3 * Sz * DSR_MC_MAX_TRI * nc);
+  A((void**)&b->tflag, Sz * nt);
+  A((void**)&b->tmark, sizeof(int) * Sz * nt);
+  A((void**)&b->tpos, sizeof(int) * Sz * nt);
+  A((void**)&b->ltiles, sizeof(Tile) * Sz * ntl);
+  A((void**)&b->atiles, sizeof(Tile) * Sz * nt);
+  A((void**)&b->etiles, sizeof(Tile) * Sz * nt);
+  A((void**)&b->rtiles, sizeof(Tile) * Sz * nt);
+  A((void**)&b->desc, sizeof(ObjDesc) * Sz);
+  A((void**)&b->st, sizeof(ObjState) * Sz);
+  A((void**)&b->rb, sizeof(int) * b->n_rb);
+  for (hipEvent_t& e : b->ev)
+    if (ok && hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; ok = false; }
+  if (ok) {
+    b->offs_v = b->rb;
+    b->offs_f = b->offs_v + S + 1;
+    b->stat = b->offs_f + S + 1;
+    b->cnt = b->stat + MS_INTS;
+    b->slot_err = b->cnt + 4;
+    b->slot_viol = b->slot_err + S;
+    b->slot_redo = b->slot_viol + S;
+    b->diag = b->slot_redo + S;
+    std::vector<Tile> lt(Sz * ntl), at(Sz * nt);
+    std::vector<ObjDesc> hd(S);
+    for (int s = 0; s < S; ++s) {
+      hd[s] = ObjDesc{};
+      hd[s].n_pts = n;
+      hd[s].ray_off = s * np;
+      hd[s].n_rays = np;
+      hd[s].cand_off = s * np;
+      for (int t = 0; t < ntl; ++t) lt[(size_t)s * ntl + t] = Tile{s, 0, t * LTILE, std::min(LTILE, n - t * LTILE)};
+      for (int t = 0; t < nt; ++t) at[(size_t)s * nt + t] = Tile{s, 0, t * TILE, std::min(TILE, n - t * TILE)};
+    }
+    ok = hipMemset(b->pts, 0, sizeof(float4) * Sz * np) == hipSuccess &&
+         hipMemset(b->st, 0, sizeof(ObjState) * Sz) == hipSuccess &&
+         hipMemcpy(b->ltiles, lt.data(), sizeof(Tile) * lt.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(b->atiles, at.data(), sizeof(Tile) * at.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(b->desc, hd.data(), sizeof(ObjDesc) * Sz, hipMemcpyHostToDevice) == hipSuccess;
+    for (int s = 0; ok && s < S; ++s)
+      ok = hipMemcpy(b->pts + (size_t)s * np, m->pts, sizeof(float4) * n, hipMemcpyDeviceToDevice) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+  }
+  if (!ok) {
+    mesh_batch_free(b);
+    return false;
+  }
+  b->hrb.resize(b->n_rb);
+  m->mb = b;
+  return true;
+}
+
+// may this decoder's lite values settle the sign of a grid?  (DSR_MESH_LITE=0: a plain runtime
+// switch, read per call)
+static bool mesh_sign_pass(const dsr_decoder* dec) {
+  const char* e = getenv("DSR_MESH_LITE");
+  if (e && atoi(e) == 0) return false;
+  return dec->info.lite_eligible && !is_variant(dec->D);
+}
+
+// one pass: ns codes (zero-padded to 64 floats each in b->hcodes) through fold, sign pass, exact
+// tiles and marching cubes; the read-back record is in b->hrb when it returns (stream idle)
+static int mesh_pass(dsr_mesher* m, int ns, float level, bool sign, const ErtArgs& hooks) {
+  dsr_ctx* ctx = m->ctx;
+  MeshBatch* b = m->mb;
+  hipStream_t s = ctx->stream;
+  const DevDecoder& D = m->dec->D;
+  const int d = m->d, n = m->n, nt = m->nt, np = b->np, nc = (d - 1) * (d - 1) * (d - 1), ne = 3 * n;
+  const int B = 256;
+  DSR_CHECK(ctx, hipMemcpyAsync(b->codes, b->hcodes.data(), sizeof(float) * CODE * ns, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_mesh_begin, dim3(1), dim3(256), 0, s, b->rb, b->n_rb, b->cnt, ns * b->ntl, ns * nt);
+  DSR_CHECK(ctx, hipEventRecord(b->ev[0], s));
+  for (int c = 0; c < ns; ++c)
+    hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, (const float*)b->codes + (size_t)c * CODE,
+                       b->b0 + (size_t)c * HID, b->b4 + (size_t)c * HID);
+  const FwdKernel fwdk = fwd_kernel_for(D, query_fwd_variant());
+  const ErtArgs EX{nullptr, 1, 0.f, nullptr, nullptr};
+  const MaskArgs MX{nullptr, nullptr, nullptr, nullptr};
+  const int egrid = std::min(ctx->n_cu, ns * nt);
+  if (sign) {
+    DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)ns * np, s));
+    ErtArgs E = hooks;                   // lag, perturb (test hook)
+    E.dead = b->flag;                    // M = 1, level-free classes: "full" is y <= 0, written and unused
+    E.M = 1;
+    E.nth = 0.f;
+    E.st = b->st;                        // zeroed: margin 0, so only NaN / the range guard flag `refine`
+    E.refine = b->refine;
+    E.audit = 0;
+    E.diag = b->diag;
+    hipLaunchKernelGGL(lite_kernel(), dim3(std::min(ctx->n_cu, ns * b->ntl)), dim3(512), 0, s, D,
+                       (const Tile*)b->ltiles, (const int*)b->cnt, (const ObjDesc*)b->desc, (const float4*)b->pts,
+                       (const float*)b->b0, (const float*)b->b4, b->lite, E);
+    DSR_CHECK(ctx, hipEventRecord(b->ev[1], s));
+    hipLaunchKernelGGL(k_mesh_mark, dim3((nt + 3) / 4, ns), dim3(256), 0, s, (const float*)b->lite,
+                       (const unsigned char*)b->refine, d, n, np, nt, level, MESH_MARGIN, b->tflag, b->tmark, b->stat);
+    mc_scan(s, b->tmark, ns * nt, b->tpos, b->bsum, b->cnt + 2);
+    hipLaunchKernelGGL(k_mesh_compact, dim3((ns * nt + B - 1) / B), dim3(B), 0, s, (const int*)b->tmark,
+                       (const int*)b->tpos, nt, n, ns * nt, b->etiles);
+    hipLaunchKernelGGL(fwdk, dim3(egrid), dim3(512), 0, s, D, (const Tile*)b->etiles, (const int*)(b->cnt + 2),
+                       (const ObjDesc*)b->desc, (const float4*)b->pts, (const float*)b->b0, (const float*)b->b4,
+                       b->vol, (unsigned*)nullptr, EX, MX);
+    hipLaunchKernelGGL(k_mesh_merge, dim3((n + 255) / 256, ns), dim3(256), 0, s, (const float*)b->lite,
+                       (const unsigned char*)b->refine, (const unsigned char*)b->tflag, n, np, nt, level,
+                       MESH_MARGIN, b->vol, b->slot_err, b->slot_viol);
+    hipLaunchKernelGGL(k_mesh_redo, dim3(1), dim3(MC_SCAN_BLOCK), 0, s, (const int*)b->slot_err,
+                       (const int*)b->slot_viol, ns, nt, n, MESH_MARGIN, (const unsigned char*)b->tflag, b->rtiles,
+                       b->cnt + 3, b->slot_redo, b->stat);
+    // the rejected slots' remaining tiles (an empty table when the guard holds: the blocks return)
+    hipLaunchKernelGGL(fwdk, dim3(egrid), dim3(512), 0, s, D, (const Tile*)b->rtiles, (const int*)(b->cnt + 3),
+                       (const ObjDesc*)b->desc, (const float4*)b->pts, (const float*)b->b0, (const float*)b->b4,
+                       b->vol, (unsigned*)nullptr, EX, MX);
+  } else {
+    DSR_CHECK(ctx, hipEventRecord(b->ev[1], s));
+    hipLaunchKernelGGL(fwdk, dim3(egrid), dim3(512), 0, s, D, (const Tile*)b->atiles, (const int*)(b->cnt + 1),
+                       (const ObjDesc*)b->desc, (const float4*)b->pts, (const float*)b->b0, (const float*)b->b4,
+                       b->vol, (unsigned*)nullptr, EX, MX);
+  }
+  DSR_CHECK(ctx, hipEventRecord(b->ev[2], s));
+  hipLaunchKernelGGL(k_mcb_edges, dim3((n + B - 1) / B, ns), dim3(B), 0, s, (const float*)b->vol, d, np, level, b->flag);
+  hipLaunchKernelGGL(k_mcb_cells, dim3((nc + B - 1) / B, ns), dim3(B), 0, s, (const float*)b->vol, d, np, level, b->ntri);
+  mc_scan(s, b->flag, ns * ne, b->vidx, b->bsum, b->offs_v + ns);
+  mc_scan(s, b->ntri, ns * nc, b->toff, b->bsum, b->offs_f + ns);
+  hipLaunchKernelGGL(k_mcb_verts, dim3((ne + B - 1) / B, ns), dim3(B), 0, s, (const float*)b->vol, d, np, level,
+                     2.0 / (double)(d - 1), (const int*)b->flag, (const int*)b->vidx, b->verts, b->offs_v);
+  hipLaunchKernelGGL(k_mcb_faces, dim3((nc + B - 1) / B, ns), dim3(B), 0, s, (const float*)b->vol, d, np, level,
+                     (const int*)b->vidx, (const int*)b->toff, b->faces, b->offs_f);
+  DSR_CHECK(ctx, hipGetLastError());
+  DSR_CHECK(ctx, hipEventRecord(b->ev[3], s));
+  DSR_CHECK(ctx, hipMemcpyAsync(b->hrb.data(), b->rb, sizeof(int) * b->n_rb, hipMemcpyDeviceToHost, s));
+  DSR_CHECK(ctx, hipStreamSynchronize(s));
+  b->last_ns = ns;
+  b->last_sign = sign;
+  return 0;
+}
+
+int dsr_mesher_run_batch(dsr_mesher* m, int n_codes, const float* codes, float level, float* verts, int vcap,
+                         int* faces, int fcap, int* vert_off, int* face_off) {
+  if (!m || !vert_off || !face_off || (n_codes > 0 && !codes)) return fail(m ? m->ctx : nullptr, "null argument");
+  if (n_codes < 0) return fail(m->ctx, "n_codes must not be negative");
+  dsr_ctx* ctx = m->ctx;
+  dsr_mesher_stats& st = m->st;
+  st = dsr_mesher_stats{};
+  st.margin = MESH_MARGIN;
+  vert_off[0] = face_off[0] = 0;
+  if (n_codes == 0) return 0;
+  if (!variant_kernels_ok(m->dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  hipSetDevice(ctx->device);
+  const int cap = (int)std::max<size_t>(1, std::min<size_t>(MESH_MAX_SLOTS, MESH_BUDGET / mesh_slot_bytes(m)));
+  int want = std::min(n_codes, cap);
+  if (!m->mb || m->mb->S < want) {
+    DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    while (!mesh_batch_alloc(m, want)) {           // out of memory: fewer slots, more passes
+      if (want == 1) return fail(ctx, "hipMalloc failed (mesher batch)");
+      want = (want + 1) / 2;
+    }
+  }
+  MeshBatch* b = m->mb;
+  const int S = b->S, L = m->dec->code_len;
+  const bool hooks = test_hooks();
+  const bool sign = mesh_sign_pass(m->dec);
+  const ErtArgs E = lite_settings(hooks);
+  const bool multi = n_codes > S;
+  st.n_codes = n_codes;
+  st.slots = S;
+  st.sign_pass = sign ? 1 : 0;
+  st.test_hooks = hooks ? 1 : 0;
+  b->hv.clear();
+  b->hf.clear();
+  long long tv = 0, tf = 0;                          // running totals
+  bool fits = true;
+  for (int c0 = 0; c0 < n_codes; c0 += S) {
+    const int ns = std::min(S, n_codes - c0);
+    b->hcodes.assign((size_t)ns * CODE, 0.f);        // a 32-D code runs padded with zeros
+    for (int c = 0; c < ns; ++c)
+      std::memcpy(b->hcodes.data() + (size_t)c * CODE, codes + (size_t)(c0 + c) * L, sizeof(float) * L);
+    const int rc = mesh_pass(m, ns, level, sign, E);
+    if (rc != 0) return rc;
+    const int* r = b->hrb.data();
+    const int *ov = r, *of = r + S + 1, *stat = of + S + 1, *cnt = stat + MS_INTS, *serr = cnt + 4,
+              *sviol = serr + S, *diag = sviol + 2 * S;
+    const int pv = ov[ns], pf = of[ns];
+    if (tv + pv > INT_MAX || tf + pf > INT_MAX) return fail(ctx, "mesh batch larger than 2^31 vertices or faces");
+    for (int c = 0; c <= ns; ++c) {
+      vert_off[c0 + c] = (int)tv + (c < ns ? ov[c] : pv);
+      face_off[c0 + c] = (int)tf + (c < ns ? of[c] : pf);
+    }
+    ++st.n_passes;
+    st.all_tiles += ns * m->nt;
+    if (sign) {
+      st.lite_tiles += ns * b->ntl;
+      st.exact_tiles += cnt[2];
+      st.audit_tiles += stat[MS_AUDIT_TILES];
+      st.redo_tiles += stat[MS_REDO_TILES];
+      st.redone_codes += stat[MS_REDO_SLOTS];
+      st.lite_broken_blocks += diag[STD_BROKEN];
+      for (int c = 0; c < ns; ++c) {
+        st.violations += sviol[c];
+        float e;
+        std::memcpy(&e, &serr[c], sizeof(float));
+        st.max_lite_err = std::max(st.max_lite_err, (double)e);
+      }
+    } else {
+      st.exact_tiles += ns * m->nt;
+    }
+    float ms[3] = {0.f, 0.f, 0.f};
+    for (int k = 0; k < 3; ++k)
+      if (hipEventElapsedTime(&ms[k], b->ev[k], b->ev[k + 1]) != hipSuccess) (void)hipGetLastError();
+    st.lite_ms += ms[0];
+    st.exact_ms += ms[1];
+    st.mc_ms += ms[2];
+    // copy-out: a one-pass call straight to the caller once it is known to fit; a call of several
+    // passes through host staging, so that nothing is written when a later pass does not fit
+    fits = fits && tv + pv <= vcap && tf + pf <= fcap && (tv + pv == 0 || verts) && (tf + pf == 0 || faces);
+    if (fits) {
+      float* dv = verts;
+      int* df = faces;
+      if (multi) {
+        b->hv.resize((size_t)(tv + pv) * 3);
+        b->hf.resize((size_t)(tf + pf) * 3);
+        dv = b->hv.data();
+        df = b->hf.data();
+      }
+      if (pv > 0) DSR_CHECK(ctx, hipMemcpy(dv + (size_t)tv * 3, b->verts, sizeof(float) * 3 * pv, hipMemcpyDeviceToHost));
+      if (pf > 0) DSR_CHECK(ctx, hipMemcpy(df + (size_t)tf * 3, b->faces, sizeof(int) * 3 * pf, hipMemcpyDeviceToHost));
+    }
+    tv += pv;
+    tf += pf;
+  }
+  if (!fits) {
+    fail(ctx, "meshes larger than the given capacity");
+    return -5;
+  }
+  if (multi) {
+    if (tv > 0) std::memcpy(verts, b->hv.data(), sizeof(float) * 3 * (size_t)tv);
+    if (tf > 0) std::memcpy(faces, b->hf.data(), sizeof(int) * 3 * (size_t)tf);
+  }
+  return 0;
+}
+
+int dsr_mesher_stats_get(const dsr_mesher* m, dsr_mesher_stats* st) {
+  if (!m || !st) return -2;
+  *st = m->st;
+  return 0;
+}
+
+int dsr_mesher_peek(dsr_mesher* m, int slot, float* lite_vol, float* final_vol, unsigned char* tile_flags) {
+  if (!m) return -2;
+  dsr_ctx* ctx = m->ctx;
+  MeshBatch* b = m->mb;
+  if (!b || slot < 0 || slot >= b->last_ns) return fail(ctx, "no such slot in the last pass");
+  if ((lite_vol || tile_flags) && !b->last_sign) return fail(ctx, "the last pass ran without the sign pass");
+  hipSetDevice(ctx->device);
+  DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t o = (size_t)slot * b->np;
+  if (lite_vol) DSR_CHECK(ctx, hipMemcpy(lite_vol, b->lite + o, sizeof(float) * m->n, hipMemcpyDeviceToHost));
+  if (final_vol) DSR_CHECK(ctx, hipMemcpy(final_vol, b->vol + o, sizeof(float) * m->n, hipMemcpyDeviceToHost));
+  if (tile_flags) DSR_CHECK(ctx, hipMemcpy(tile_flags, b->tflag + (size_t)slot * m->nt, m->nt, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int dsr_sdf_eval(dsr_ctx* ctx, const dsr_decoder* dec, const float* code, const float* pts, int n,

@@ -14,7 +14,8 @@
  *                              reconstruct_multi, sdf_eval with and without the Jacobian,
  *                              pose-only single and batched (including an empty object), the
  *                              mesher (and dsr_mc_volume on its decoded grid) with ample and
- *                              with too small capacities, forced audit
+ *                              with too small capacities, the batch call (dsr_mesher_run_batch:
+ *                              ample and too small totals, n = 0) against it, forced audit
  *                              violations and their spare-iteration redo (test hooks), and the
  *                              error paths of a live context.  Exit status 0 = every check held.
  */
@@ -81,6 +82,12 @@ static void no_device_paths(void) {
         "batch calls on NULL accepted");
   CHECK(dsr_batch_download(NULL, NULL) < 0 && dsr_batch_stats(NULL, NULL) < 0, "batch NULL accepted");
   CHECK(dsr_mesher_destroy(NULL) == 0, "mesher_destroy(NULL)");
+  {
+    int vo[2], fo[2];
+    CHECK(dsr_mesher_run_batch(NULL, 1, NULL, 0.f, NULL, 0, NULL, 0, vo, fo) < 0, "mesher_run_batch(NULL) accepted");
+    CHECK(dsr_mesher_run_batch(NULL, -1, NULL, 0.f, NULL, 0, NULL, 0, vo, fo) < 0, "mesher_run_batch(n = -1) accepted");
+    CHECK(dsr_mesher_stats_get(NULL, NULL) < 0 && dsr_mesher_peek(NULL, 0, NULL, NULL, NULL) < 0, "mesher NULL accepted");
+  }
   CHECK(dsr_batch_refill(NULL, 0, NULL) < 0, "refill(NULL) accepted");
   CHECK(dsr_batch_create_capacity(NULL, NULL, NULL, 1, 1, 1, 0, NULL) < 0, "create_capacity(NULL) accepted");
   CHECK(dsr_decoder_info_get(NULL, NULL) < 0, "decoder_info_get(NULL) accepted");
@@ -419,6 +426,39 @@ int main(int argc, char** argv) {
     for (int f = 0; f < 3 * nface; ++f) CHECK(F[f] >= 0 && F[f] < nvert, "face index %d", F[f]);
     CHECK(dsr_mesher_run(m, ref[0].code, 0.f, V, 1, F, 1, &nv2, &nf2) == -5, "small capacity accepted");
     CHECK(nv2 == nvert && nf2 == nface, "counts on -5");
+    /* the batch call: three codes (the first and last equal), ample and too-small totals, n = 0 */
+    {
+      float codes[3 * DSR_CODE_LEN];
+      memset(codes, 0, sizeof codes);
+      memcpy(codes, ref[0].code, sizeof(float) * DSR_CODE_LEN);
+      memcpy(codes + 2 * DSR_CODE_LEN, ref[0].code, sizeof(float) * DSR_CODE_LEN);
+      float* VB = (float*)malloc(sizeof(float) * 3 * 3 * (size_t)vcap);
+      int* FB = (int*)malloc(sizeof(int) * 3 * 3 * (size_t)fcap);
+      int vo[4] = {-1, -1, -1, -1}, fo[4] = {-1, -1, -1, -1}, vo2[4], fo2[4];
+      CHECK(dsr_mesher_run_batch(m, 3, codes, 0.f, VB, 3 * vcap, FB, 3 * fcap, vo, fo) == 0, "%s", dsr_last_error(ctx));
+      CHECK(vo[0] == 0 && fo[0] == 0 && vo[1] == nvert && fo[1] == nface, "batch offsets %d %d", vo[1], fo[1]);
+      CHECK(vo[3] - vo[2] == nvert && fo[3] - fo[2] == nface, "batch counts of the last mesh");
+      CHECK(memcmp(VB, V, sizeof(float) * 3 * (size_t)nvert) == 0 && memcmp(FB, F, sizeof(int) * 3 * (size_t)nface) == 0,
+            "batch mesh 0 differs from the mesher's");
+      CHECK(memcmp(VB + 3 * (size_t)vo[2], V, sizeof(float) * 3 * (size_t)nvert) == 0 &&
+            memcmp(FB + 3 * (size_t)fo[2], F, sizeof(int) * 3 * (size_t)nface) == 0, "batch mesh 2 differs");
+      dsr_mesher_stats ms;
+      CHECK(dsr_mesher_stats_get(m, &ms) == 0 && ms.n_codes == 3 && ms.n_passes == 1 && ms.violations == 0 &&
+            ms.redone_codes == 0 && ms.lite_broken_blocks == 0 && ms.exact_tiles <= ms.all_tiles, "mesher stats");
+      VB[0] = 12345.f;
+      FB[0] = -7;
+      CHECK(dsr_mesher_run_batch(m, 3, codes, 0.f, VB, vo[3] - 1, FB, 3 * fcap, vo2, fo2) == -5, "one vertex short accepted");
+      CHECK(memcmp(vo, vo2, sizeof vo) == 0 && memcmp(fo, fo2, sizeof fo) == 0, "offsets on -5");
+      CHECK(VB[0] == 12345.f && FB[0] == -7, "output written on -5");
+      CHECK(dsr_mesher_run_batch(m, 3, codes, 0.f, VB, 3 * vcap, FB, fo[3] - 1, vo2, fo2) == -5, "one face short accepted");
+      vo2[0] = fo2[0] = -1;
+      CHECK(dsr_mesher_run_batch(m, 0, NULL, 0.f, NULL, 0, NULL, 0, vo2, fo2) == 0 && vo2[0] == 0 && fo2[0] == 0, "n = 0");
+      CHECK(dsr_mesher_run_batch(m, -1, codes, 0.f, VB, 1, FB, 1, vo2, fo2) < 0, "n = -1 accepted");
+      CHECK(dsr_mesher_run_batch(m, 3, NULL, 0.f, VB, 1, FB, 1, vo2, fo2) < 0, "NULL codes accepted");
+      CHECK(dsr_mesher_peek(m, 3, NULL, NULL, NULL) < 0, "peek beyond the last pass accepted");
+      free(VB);
+      free(FB);
+    }
     CHECK(dsr_mesher_destroy(m) == 0, "mesher_destroy");
     /* the same grid decoded by dsr_sdf_eval, meshed by dsr_mc_volume: the mesher's mesh */
     float* vol = (float*)malloc(sizeof(float) * nv);

@@ -69,7 +69,7 @@ class Trace(C.Structure):
                 ("n_decoded", IP), ("n_refined", IP)]
 
 
-ABI_VERSION = 11         # include/dsr.h DSR_ABI_VERSION
+ABI_VERSION = 12         # include/dsr.h DSR_ABI_VERSION
 BATCH_GRAPH = 1          # include/dsr.h DSR_BATCH_GRAPH
 GATHER_HOST, GATHER_RCCL = 0, 1   # include/dsr.h DSR_GATHER_* (dsr_reconstruct_multi_ex)
 
@@ -98,6 +98,16 @@ class DecoderInfo(C.Structure):
     _fields_ = [("code_len", C.c_int), ("lite_eligible", C.c_int), ("lite_probe_ratio", C.c_double),
                 ("lite_probe_max_err", C.c_double), ("lite_probe_max_err_all", C.c_double),
                 ("probe_points", C.c_int), ("probe_codes", C.c_int), ("probe_ms", C.c_double)]
+
+class MesherStats(C.Structure):
+    """dsr_mesher_stats: the last dsr_mesher_run_batch call of a mesher (include/dsr.h)."""
+    _fields_ = [("n_codes", C.c_int), ("n_passes", C.c_int), ("slots", C.c_int), ("sign_pass", C.c_int),
+                ("margin", C.c_float), ("lite_tiles", C.c_int), ("all_tiles", C.c_int),
+                ("exact_tiles", C.c_int), ("audit_tiles", C.c_int), ("redo_tiles", C.c_int),
+                ("violations", C.c_int), ("redone_codes", C.c_int), ("lite_broken_blocks", C.c_int),
+                ("test_hooks", C.c_int), ("max_lite_err", C.c_double), ("lite_ms", C.c_double),
+                ("exact_ms", C.c_double), ("mc_ms", C.c_double)]
+
 
 #: dsr_batch_lite_diag record layout (csrc/dsr_dev.hpp: STD_*)
 LITE_DIAG_FIELDS = ("broken_blocks", "recorded", "block", "wave", "counter", "target", "observed", "tile_iter",
@@ -149,6 +159,9 @@ SIGNATURES = {
     "dsr_mesher_create": (C.c_int, [C.c_void_p, C.c_void_p, FP, C.c_int, C.POINTER(C.c_void_p)]),
     "dsr_mesher_run": (C.c_int, [C.c_void_p, FP, C.c_float, FP, C.c_int, IP, C.c_int, IP, IP]),
     "dsr_mesher_destroy": (C.c_int, [C.c_void_p]),
+    "dsr_mesher_run_batch": (C.c_int, [C.c_void_p, C.c_int, FP, C.c_float, FP, C.c_int, IP, C.c_int, IP, IP]),
+    "dsr_mesher_stats_get": (C.c_int, [C.c_void_p, C.POINTER(MesherStats)]),
+    "dsr_mesher_peek": (C.c_int, [C.c_void_p, C.c_int, FP, FP, C.POINTER(C.c_ubyte)]),
     "dsr_mc_volume": (C.c_int, [C.c_void_p, FP, C.c_int, C.c_float, FP, C.c_int, IP, C.c_int, IP, IP]),
 }
 

@@ -58,10 +58,17 @@ def extract_map_objects(map_dir, mesh_extractor):
     (mesh of the code through `mesh_extractor`, a reconstruct.optimizer.MeshExtractor)."""
     save_dir = os.path.join(map_dir, "objects")
     os.makedirs(save_dir, exist_ok=True)
+    objs = read_map_objects(os.path.join(map_dir, "MapObjects.txt"))
+    # all objects through the batch call (the same meshes bit for bit, DESIGN.md §3.6); an
+    # extractor without one meshes them one by one
+    batch = getattr(mesh_extractor, "extract_meshes_from_codes", None)
+    if batch is not None:
+        meshes = batch([code for _, _, code in objs])
+    else:
+        meshes = [mesh_extractor.extract_mesh_from_code(code) for _, _, code in objs]
     done = []
-    for oid, pose, code in read_map_objects(os.path.join(map_dir, "MapObjects.txt")):
+    for (oid, pose, _), mesh in zip(objs, meshes):
         np.save(os.path.join(save_dir, "%d.npy" % oid), pose)
-        mesh = mesh_extractor.extract_mesh_from_code(code)
         write_mesh_to_ply(mesh.vertices, mesh.faces, os.path.join(save_dir, "%d.ply" % oid))
         done.append(oid)
     return done

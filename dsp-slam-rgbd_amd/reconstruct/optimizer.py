@@ -186,8 +186,21 @@ class Optimizer(object):
         choice and returns one result per detection."""
         return KeyframeHandle(self, detections)
 
-    def reconstruct_keyframe(self, detections):
-        return self.reconstruct_keyframe_async(detections).wait()
+    def reconstruct_keyframe(self, detections, mesher=None):
+        """``reconstruct_keyframe_async(detections).wait()``.  With ``mesher`` (a
+        :class:`MeshExtractor`) the good objects are meshed by one batch call
+        (LocalMapping_util.cc:197, 429 mesh every successful reconstruction) and every result
+        carries ``vertices`` / ``faces`` (``None`` for a failed object)."""
+        res = self.reconstruct_keyframe_async(detections).wait()
+        if mesher is None:
+            return res
+        good = [i for i, r in enumerate(res) if r["is_good"]]
+        meshes = mesher.extract_meshes_from_codes([res[i]["code"] for i in good])
+        for r in res:
+            r["vertices"] = r["faces"] = None
+        for i, mesh in zip(good, meshes):
+            res[i]["vertices"], res[i]["faces"] = mesh.vertices, mesh.faces
+        return res
 
     MAX_SLOTS = 4
     # A slot batch is laid out for max_obj x max_rays x M ray samples whatever the fill, and every
@@ -539,3 +552,52 @@ class MeshExtractor(object):
                                          self._verts.shape[0], L.iptr(self._faces), self._faces.shape[0],
                                          C.byref(nv), C.byref(nf)), "dsr_mesher_run")
         return ForceKeyErrorDict(vertices=self._verts[:nv.value].copy(), faces=self._faces[:nf.value].copy())
+
+    def extract_meshes_from_codes(self, codes, level=0.0):
+        """The meshes of several codes from one call (dsr_mesher_run_batch): one lite decode of
+        all grids settles the sign away from the surface, exact tiles cover the band, marching
+        cubes runs over all of them at once.  Each mesh is bitwise the one
+        ``extract_mesh_from_code`` gives.  The output buffers grow to what a call needed (one
+        retry after a -5), not to the worst case times the number of codes."""
+        n = len(codes)
+        if n == 0:
+            return []
+        ctx = self.decoder.ctx
+        cs = np.ascontiguousarray(np.stack([_code(c, self.code_len) for c in codes]), np.float32)
+        voff = np.zeros(n + 1, np.int32)
+        foff = np.zeros(n + 1, np.int32)
+        bv, bf = getattr(self, "_bverts", None), getattr(self, "_bfaces", None)
+        if bv is None:
+            d = self.voxels_dim                       # a first guess: a closed surface of ~d^2 cells per code
+            bv = np.zeros((max(1024, 8 * d * d * n), 3), np.float32)
+            bf = np.zeros((max(2048, 16 * d * d * n), 3), np.int32)
+        for attempt in range(2):
+            rc = ctx.lib.dsr_mesher_run_batch(self._h, n, L.fptr(cs), float(level), L.fptr(bv), bv.shape[0],
+                                              L.iptr(bf), bf.shape[0], L.iptr(voff), L.iptr(foff))
+            if rc != -5 or attempt == 1:
+                break
+            bv = np.zeros((max(int(voff[n]), bv.shape[0]), 3), np.float32)
+            bf = np.zeros((max(int(foff[n]), bf.shape[0]), 3), np.int32)
+        self._bverts, self._bfaces = bv, bf
+        ctx.check(rc, "dsr_mesher_run_batch")
+        return [ForceKeyErrorDict(vertices=bv[voff[i]:voff[i + 1]].copy(), faces=bf[foff[i]:foff[i + 1]].copy())
+                for i in range(n)]
+
+    def stats(self):
+        """dsr_mesher_stats of the last ``extract_meshes_from_codes`` call, as a dict."""
+        st = L.MesherStats()
+        rc = self.decoder.ctx.lib.dsr_mesher_stats_get(self._h, C.byref(st))
+        if rc != 0:
+            raise L.DsrError(f"dsr_mesher_stats_get failed ({rc})")
+        return {k: getattr(st, k) for k, _ in L.MesherStats._fields_}
+
+    def peek(self, slot):
+        """Diagnostic (dsr_mesher_peek): the lite volume, the merged volume and the 64-point tile
+        flags (1 needed, 2 audit) of one slot of the last pass."""
+        ctx = self.decoder.ctx
+        n = self.voxels_dim ** 3
+        lite, final = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        flags = np.zeros((n + 63) // 64, np.uint8)
+        ctx.check(ctx.lib.dsr_mesher_peek(self._h, int(slot), L.fptr(lite), L.fptr(final),
+                                          flags.ctypes.data_as(C.POINTER(C.c_ubyte))), "dsr_mesher_peek")
+        return lite, final, flags

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DSR_ABI_VERSION 11
+#define DSR_ABI_VERSION 12
 #define DSR_MAX_LAYERS 16
 #define DSR_CODE_LEN 64
 
@@ -294,6 +294,53 @@ int dsr_mesher_create(dsr_ctx* ctx, const dsr_decoder* dec, const float* grid_pt
 int dsr_mesher_run(dsr_mesher* m, const float* code, float level, float* verts, int vcap, int* faces,
                    int fcap, int* n_verts, int* n_faces);
 int dsr_mesher_destroy(dsr_mesher* m);
+
+/* ---- batched mesh extraction (ABI 12): the meshes of n_codes codes (n_codes x code_len floats)
+ * from one call, bitwise those of n_codes dsr_mesher_run calls.  The codes run in passes of up to
+ * 16 slots (fewer when a pass's device buffers would exceed 2 GiB), each pass on the context
+ * stream with one host synchronisation: one lite (fp16) decode of all grids settles the
+ * predicate v < level away from the surface, whole 64-point tiles of dsr_mesher_run's tiling are
+ * decoded exactly where a lite value lies within the margin of the level or next to a sign
+ * change, audited tiles guard the margin, and a slot the audit rejects is decoded exactly in
+ * full.  Decoders that are not lite-eligible (dsr_decoder_info) and runs under
+ * DSR_MESH_LITE=0 decode every tile exactly; batching and the single synchronisation remain.
+ * Vertices and faces of all meshes come back concatenated: mesh i owns vertices
+ * [vert_off[i], vert_off[i+1]) and faces [face_off[i], face_off[i+1]), face indices local to
+ * their mesh.  vcap / fcap are total capacities; when one is too small the offsets are still
+ * filled, the status is -5 and nothing is copied.  n_codes == 0 returns at once. */
+int dsr_mesher_run_batch(dsr_mesher* m, int n_codes, const float* codes, float level, float* verts,
+                         int vcap, int* faces, int fcap, int* vert_off, int* face_off);
+
+/* the last dsr_mesher_run_batch call of a mesher */
+typedef struct {
+  int n_codes;
+  int n_passes;
+  int slots;                      /* codes per pass the mesher's buffers hold */
+  int sign_pass;                  /* 1: the lite pass ran; 0: every tile decoded exactly (decoder not
+                                     lite-eligible, or DSR_MESH_LITE=0) */
+  float margin;                   /* m: band half-width around the level (0.01) */
+  int lite_tiles;                 /* 128-point tiles of the lite pass */
+  int all_tiles;                  /* 64-point tiles of all codes' grids */
+  int exact_tiles;                /* of which decoded exactly by the band pass (needed + audit) */
+  int audit_tiles;                /* ... decoded as audit only */
+  int redo_tiles;                 /* tiles decoded by the redo of rejected codes */
+  int violations;                 /* decoded voxels outside the band whose exact side of the level
+                                     differs from the lite side */
+  int redone_codes;               /* codes redone with every tile exact (a violation, or a lite
+                                     error above margin / 4) */
+  int lite_broken_blocks;         /* lite-pass workgroups whose event wait expired (dsr_stats) */
+  int test_hooks;                 /* DSR_TEST_HOOKS=1 was set: DSR_LITE_PERTURB etc. were honoured */
+  double max_lite_err;            /* max |lite - exact| over the decoded voxels */
+  double lite_ms, exact_ms, mc_ms;   /* device events: fold + lite pass; mark, exact passes and
+                                        merge; marching cubes (summed over the passes) */
+} dsr_mesher_stats;
+int dsr_mesher_stats_get(const dsr_mesher* m, dsr_mesher_stats* st);
+
+/* diagnostic: slot `slot` of the last pass of the last dsr_mesher_run_batch call — its lite volume
+ * and final (merged) volume (vol_dim^3 floats each) and the flags of its 64-point tiles
+ * (ceil(vol_dim^3 / 64) bytes: 1 = needed, 2 = audit, 0 = left to the lite value).  Any output may
+ * be NULL; the lite volume and the flags exist only when the sign pass ran (-2 otherwise). */
+int dsr_mesher_peek(dsr_mesher* m, int slot, float* lite_vol, float* final_vol, unsigned char* tile_flags);
 
 /* ---- marching cubes on a caller's volume: replaces convert_sdf_voxels_to_mesh
  * (utils.py:119-140) called on its own.  `vol` is the (vol_dim, vol_dim, vol_dim) SDF
