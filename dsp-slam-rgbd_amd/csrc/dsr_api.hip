@@ -277,8 +277,18 @@ struct dsr_batch {
     int* scnt = nullptr;              // chunked render passes: samples, in-ball samples per chunk
     int2* och = nullptr;              // per object: first chunk, chunks (the chunked path's tile tables)
     int n_rch = 0;
+    int t0 = 0, nt = 0;               // tied batches: the group's tied objects (tie[t0 .. t0 + nt))
   };
   std::vector<Group> groups;
+  // Tied batches (dsr_reconstruct_views): the views of one object are consecutive members, the
+  // reference view first.  tie[i] = (leader member relative to its group's first member, views)
+  // of tied object i; cview[member] = inverse(t_view_ref); fail_view[i] = the view that failed
+  // object i or -1.  k_solve_views replaces k_solve, k_views_pose re-derives the members' poses.
+  int n_tied = 0;                     // 0: an ordinary batch
+  bool tie_multi = false;             // some object has more than one view
+  int2* tie = nullptr;
+  float* cview = nullptr;
+  int* fail_view = nullptr;
   hipEvent_t fork_ev = nullptr;
   hipEvent_t done_ev = nullptr;  // recorded after every run (dsr_batch_query)
   std::vector<hipEvent_t> join_ev;
@@ -1075,7 +1085,8 @@ static bool graph_enabled();
 
 static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p,
                              int n_obj, const dsr_object_in* in, bool trace, dsr_batch** out,
-                             bool one_group = false) {
+                             bool one_group = false, const std::vector<int>* views = nullptr,
+                             const float* cview = nullptr) {
   if (!ctx || !dec || !p || !out || (n_obj > 0 && !in)) return fail(ctx, "null argument");
   *out = nullptr;
   if (n_obj <= 0) return fail(ctx, "n_obj must be > 0");
@@ -1114,11 +1125,29 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
     int G = e ? atoi(e) : (graph_enabled() || one_group) ? 1 : ((n_obj <= 16 && cand_est >= 500000) ? 4 : 2);
     G = std::max(1, std::min(std::min(G, MAX_GROUPS), n_obj));
     if (fwd_variant() & 1) G = 1;             // the XCD soft sync assumes one fwd grid at a time
-    for (int g = 0; g < G; ++g) {
-      dsr_batch::Group gr;
-      gr.o0 = (int)((long)n_obj * g / G);
-      gr.n = (int)((long)n_obj * (g + 1) / G) - gr.o0;
-      b->groups.push_back(gr);
+    if (views) {
+      // a tied batch: the same split over the tied objects, so that a group boundary is an
+      // object boundary and every view of an object runs on one stream (k_solve_views reads all
+      // of them in stream order); with one view per object these are the ranges below
+      const int nt = (int)views->size();
+      std::vector<int> first(nt + 1, 0);
+      for (int i = 0; i < nt; ++i) first[i + 1] = first[i] + (*views)[i];
+      G = std::min(G, nt);
+      for (int g = 0; g < G; ++g) {
+        dsr_batch::Group gr;
+        gr.t0 = (int)((long)nt * g / G);
+        gr.nt = (int)((long)nt * (g + 1) / G) - gr.t0;
+        gr.o0 = first[gr.t0];
+        gr.n = first[gr.t0 + gr.nt] - gr.o0;
+        b->groups.push_back(gr);
+      }
+    } else {
+      for (int g = 0; g < G; ++g) {
+        dsr_batch::Group gr;
+        gr.o0 = (int)((long)n_obj * g / G);
+        gr.n = (int)((long)n_obj * (g + 1) / G) - gr.o0;
+        b->groups.push_back(gr);
+      }
     }
     if (dec->D.ln_mask)
       for (int g = 0; g < G; ++g)
@@ -1363,6 +1392,18 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
   ALLOC(b->diag, sizeof(int) * STD_INTS);
   ALLOC(b->counts, sizeof(int) * COUNT_STRIDE * (size_t)std::max(1, b->loop_iters) * n_obj);
   ALLOC(b->out, sizeof(dsr_object_out) * n_obj);
+  std::vector<int2> htie;
+  if (views) {
+    b->n_tied = (int)views->size();
+    for (const auto& gr : b->groups)
+      for (int i = gr.t0, o = gr.o0; i < gr.t0 + gr.nt; o += (*views)[i], ++i) {
+        htie.push_back(make_int2(o - gr.o0, (*views)[i]));
+        b->tie_multi = b->tie_multi || (*views)[i] > 1;
+      }
+    ALLOC(b->tie, sizeof(int2) * htie.size());
+    ALLOC(b->cview, sizeof(float) * 16 * n_obj);
+    ALLOC(b->fail_view, sizeof(int) * htie.size());
+  }
   if (trace) {
     const size_t it = std::max(1, b->iters);
     ALLOC(b->tr_H, sizeof(float) * TRACE_H_STRIDE * it * n_obj);
@@ -1379,7 +1420,9 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
       !up(b->is_oc, hoc.data(), sizeof(int) * n_obj) ||
       !up(b->pts, hpts.data(), sizeof(float) * hpts.size()) ||
       !up(b->rays, hrays.data(), sizeof(float) * hrays.size()) ||
-      !up(b->dobs, hdobs.data(), sizeof(float) * hdobs.size())) {
+      !up(b->dobs, hdobs.data(), sizeof(float) * hdobs.size()) ||
+      (views && (!up(b->tie, htie.data(), sizeof(int2) * htie.size()) ||
+                 !up(b->cview, cview, sizeof(float) * 16 * n_obj)))) {
     dsr_batch_destroy(b);
     return fail(ctx, "hipMemcpy (inputs) failed");
   }
@@ -1645,6 +1688,11 @@ static int batch_enqueue(dsr_batch* b, bool timing) {
   hipLaunchKernelGGL(k_init_state, dim3(n), dim3(64), 0, ctx->stream, n, b->t_in, b->is_oc, b->z_in, b->st,
                      b->zbuf, b->iters);
   DSR_CHECK(ctx, hipMemsetAsync(b->diag, 0, sizeof(int) * STD_INTS, ctx->stream));
+  if (b->n_tied) DSR_CHECK(ctx, hipMemsetAsync(b->fail_view, 0xff, sizeof(int) * b->n_tied, ctx->stream));
+  if (b->tie_multi)               // the views' start poses from their leaders' (before the groups fork)
+    for (const auto& gr : b->groups)
+      hipLaunchKernelGGL(k_views_pose, dim3(gr.nt), dim3(64), 0, ctx->stream, (const int2*)b->tie + gr.t0,
+                         b->st + gr.o0, (const float*)b->cview + (size_t)gr.o0 * 16);
   b->spare_run = false;
   return batch_enqueue_iters(b, timing, 0, b->iters);
 }
@@ -1804,6 +1852,16 @@ static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
       float* sred = b->sred + (size_t)o0 * SRED_STRIDE;
       hipLaunchKernelGGL(k_reduce_slots, dim3(ng * SLOT_BLOCKS), dim3(256), 0, s, desc, st, b->slots, sred, it,
                          b->counts + (size_t)o0 * COUNT_STRIDE, n);
+      if (b->n_tied) {                           // one solve per tied object, then its views' poses
+        hipLaunchKernelGGL(k_solve_views, dim3(gr.nt), dim3(SOLVE_THREADS), 0, s, (const int2*)b->tie + gr.t0, desc,
+                           st, zbuf, P, sred, b->tr_H ? b->tr_H + (size_t)o0 * TRACE_H_STRIDE : nullptr,
+                           b->tr_v ? b->tr_v + (size_t)o0 * TRACE_V_STRIDE : nullptr,
+                           b->tr_i ? b->tr_i + (size_t)o0 * TRACE_I_STRIDE : nullptr, n, b->fail_view + gr.t0);
+        if (b->tie_multi)
+          hipLaunchKernelGGL(k_views_pose, dim3(gr.nt), dim3(64), 0, s, (const int2*)b->tie + gr.t0, st,
+                             (const float*)b->cview + (size_t)o0 * 16);
+        continue;
+      }
       hipLaunchKernelGGL(k_solve, dim3(ng), dim3(SOLVE_THREADS), 0, s, ng, desc, st, zbuf, P, sred,
                          b->tr_H ? b->tr_H + (size_t)o0 * TRACE_H_STRIDE : nullptr,
                          b->tr_v ? b->tr_v + (size_t)o0 * TRACE_V_STRIDE : nullptr,
@@ -2162,6 +2220,39 @@ int dsr_reconstruct_multi(dsr_ctx* const* ctxs, const dsr_decoder* const* decs, 
   return dsr_reconstruct_multi_ex(ctxs, decs, n_dev, p, n_obj, in, out, nullptr);
 }
 
+// The trace of a finished batch run into n_out caller records: record o is that of batch member
+// member[o] (nullptr: member o).
+static int trace_download(dsr_batch* b, int n_out, const int* member, const dsr_trace* trace) {
+  dsr_ctx* ctx = b->ctx;
+  const int it = b->iters, n_obj = b->n_obj, code_len = b->dec->code_len;
+  std::vector<float> H((size_t)TRACE_H_STRIDE * std::max(1, it) * n_obj), V((size_t)TRACE_V_STRIDE * std::max(1, it) * n_obj);
+  std::vector<int> I((size_t)TRACE_I_STRIDE * std::max(1, it) * n_obj);
+  if (hipMemcpy(H.data(), b->tr_H, sizeof(float) * H.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(V.data(), b->tr_v, sizeof(float) * V.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(I.data(), b->tr_i, sizeof(int) * I.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ctx, "trace download failed");
+  for (int o = 0; o < n_out; ++o) {
+    const dsr_trace& t = trace[o];
+    for (int e = 0; e < it; ++e) {
+      const size_t k = (size_t)e * n_obj + (member ? member[o] : o);
+      if (t.H) std::memcpy(t.H + (size_t)e * NPAR * NPAR, H.data() + k * TRACE_H_STRIDE, sizeof(float) * NPAR * NPAR);
+      const float* v = V.data() + k * TRACE_V_STRIDE;
+      if (t.b) std::memcpy(t.b + (size_t)e * NPAR, v, sizeof(float) * NPAR);
+      if (t.dx) std::memcpy(t.dx + (size_t)e * NPAR, v + NPAR, sizeof(float) * NPAR);
+      if (t.loss) t.loss[e] = v[2 * NPAR];
+      if (t.sdf_loss) t.sdf_loss[e] = v[2 * NPAR + 1];
+      if (t.render_loss) t.render_loss[e] = v[2 * NPAR + 2];
+      if (t.t_obj_cam) std::memcpy(t.t_obj_cam + (size_t)e * 16, v + 2 * NPAR + 3, sizeof(float) * 16);
+      if (t.z) std::memcpy(t.z + (size_t)e * code_len, v + 2 * NPAR + 19, sizeof(float) * code_len);
+      if (t.n_valid) t.n_valid[e] = I[k * TRACE_I_STRIDE];
+      if (t.k) t.k[e] = I[k * TRACE_I_STRIDE + 1];
+      if (t.n_decoded) t.n_decoded[e] = I[k * TRACE_I_STRIDE + 2];
+      if (t.n_refined) t.n_refined[e] = I[k * TRACE_I_STRIDE + 3];
+    }
+  }
+  return 0;
+}
+
 int dsr_reconstruct_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p, int n_obj,
                           const dsr_object_in* in, dsr_object_out* out, const dsr_trace* trace) {
   if (!out) return fail(ctx, "null output");
@@ -2170,36 +2261,99 @@ int dsr_reconstruct_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_
   if (rc) return rc;
   rc = dsr_batch_run(b);
   if (!rc) rc = dsr_batch_download(b, out);
-  if (!rc && trace) {
-    const int it = b->iters;
-    std::vector<float> H((size_t)TRACE_H_STRIDE * std::max(1, it) * n_obj), V((size_t)TRACE_V_STRIDE * std::max(1, it) * n_obj);
-    std::vector<int> I((size_t)TRACE_I_STRIDE * std::max(1, it) * n_obj);
-    if (hipMemcpy(H.data(), b->tr_H, sizeof(float) * H.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(V.data(), b->tr_v, sizeof(float) * V.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(I.data(), b->tr_i, sizeof(int) * I.size(), hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(ctx, "trace download failed");
-    } else {
-      for (int o = 0; o < n_obj; ++o) {
-        const dsr_trace& t = trace[o];
-        for (int e = 0; e < it; ++e) {
-          const size_t k = (size_t)e * n_obj + o;
-          if (t.H) std::memcpy(t.H + (size_t)e * NPAR * NPAR, H.data() + k * TRACE_H_STRIDE, sizeof(float) * NPAR * NPAR);
-          const float* v = V.data() + k * TRACE_V_STRIDE;
-          if (t.b) std::memcpy(t.b + (size_t)e * NPAR, v, sizeof(float) * NPAR);
-          if (t.dx) std::memcpy(t.dx + (size_t)e * NPAR, v + NPAR, sizeof(float) * NPAR);
-          if (t.loss) t.loss[e] = v[2 * NPAR];
-          if (t.sdf_loss) t.sdf_loss[e] = v[2 * NPAR + 1];
-          if (t.render_loss) t.render_loss[e] = v[2 * NPAR + 2];
-          if (t.t_obj_cam) std::memcpy(t.t_obj_cam + (size_t)e * 16, v + 2 * NPAR + 3, sizeof(float) * 16);
-          if (t.z) std::memcpy(t.z + (size_t)e * dec->code_len, v + 2 * NPAR + 19, sizeof(float) * dec->code_len);
-          if (t.n_valid) t.n_valid[e] = I[k * TRACE_I_STRIDE];
-          if (t.k) t.k[e] = I[k * TRACE_I_STRIDE + 1];
-          if (t.n_decoded) t.n_decoded[e] = I[k * TRACE_I_STRIDE + 2];
-          if (t.n_refined) t.n_refined[e] = I[k * TRACE_I_STRIDE + 3];
-        }
-      }
+  if (!rc && trace) rc = trace_download(b, n_obj, nullptr, trace);
+  dsr_batch_destroy(b);
+  return rc;
+}
+
+// inverse of a rigid 4x4 (x_view = t_view_ref x_ref) in fp64, rounded once: [R^T | -R^T t].
+// False unless the last row is 0 0 0 1 and R^T R = I within 1e-4 with det R > 0.
+static bool rigid_inverse(const float* t, float* out) {
+  if (t[12] != 0.f || t[13] != 0.f || t[14] != 0.f || t[15] != 1.f) return false;
+  double R[3][3], tr[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[i][j] = (double)t[i * 4 + j];
+    tr[i] = (double)t[i * 4 + 3];
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < 3; ++k) s += R[k][i] * R[k][j];
+      if (!(std::fabs(s - (i == j ? 1.0 : 0.0)) <= 1e-4)) return false;       // (NaN fails too)
+    }
+  const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                     R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+  if (!(det > 0.0)) return false;
+  for (int i = 0; i < 3; ++i) {
+    if (!std::isfinite(tr[i])) return false;
+    for (int j = 0; j < 3; ++j) out[i * 4 + j] = (float)R[j][i];
+    out[i * 4 + 3] = (float)(-(R[0][i] * tr[0] + R[1][i] * tr[1] + R[2][i] * tr[2]));
+  }
+  out[12] = out[13] = out[14] = 0.f;
+  out[15] = 1.f;
+  return true;
+}
+
+int dsr_reconstruct_views(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p, int n_obj,
+                          const dsr_views_object_in* in, dsr_object_out* out, const dsr_trace* trace,
+                          int* fail_view, dsr_stats* stats) {
+  if (n_obj > 0 && !in) return fail(ctx, "null argument");
+  if (!out) return fail(ctx, "null output");
+  if (n_obj <= 0) return fail(ctx, "n_obj must be > 0");
+  // every view one member of an ordinary batch, an object's views consecutive, view 0 first
+  // (the views are validated here, before anything needs the device; batch_create_impl checks
+  // the context, the decoder, the parameters and the members' buffers)
+  std::vector<dsr_object_in> mem;
+  std::vector<int> views(n_obj), leader(n_obj);
+  std::vector<float> cview;
+  for (int o = 0; o < n_obj; ++o) {
+    const dsr_views_object_in& x = in[o];
+    if (x.n_views < 1 || !x.views) return fail(ctx, "an object needs n_views >= 1 views");
+    if ((long long)mem.size() + x.n_views > (long long)INT_MAX / 64) return fail(ctx, "too many views");
+    views[o] = x.n_views;
+    leader[o] = (int)mem.size();
+    for (int v = 0; v < x.n_views; ++v) {
+      const dsr_view_in& w = x.views[v];
+      float c[16];
+      if (!rigid_inverse(w.t_view_ref, c))
+        return fail(ctx, "t_view_ref is not rigid (last row 0 0 0 1, R^T R = I within 1e-4, det R > 0)");
+      if (v == 0)                                // the reference view: T_0 = T, never multiplied
+        for (int i = 0; i < 16; ++i)
+          if (std::fabs(w.t_view_ref[i] - (i % 5 == 0 ? 1.f : 0.f)) > 1e-6f)
+            return fail(ctx, "view 0 is the reference view: its t_view_ref must be the identity");
+      cview.insert(cview.end(), c, c + 16);
+      dsr_object_in m{};
+      std::copy(x.t_cam_obj, x.t_cam_obj + 16, m.t_cam_obj);     // (views >= 1: k_views_pose overwrites the pose)
+      m.pts = w.pts; m.n_pts = w.n_pts;
+      m.rays = w.rays; m.n_rays = w.n_rays;
+      m.depth = w.depth; m.n_depth = w.n_depth;
+      m.code = x.code;
+      m.pose_is_obj_cam = x.pose_is_obj_cam;
+      mem.push_back(m);
     }
   }
+  const int n_mem = (int)mem.size();
+  dsr_batch* b = nullptr;
+  int rc = batch_create_impl(ctx, dec, p, n_mem, mem.data(), trace != nullptr, &b, false, &views, cview.data());
+  if (rc) return rc;
+  std::vector<dsr_object_out> mout(n_mem);
+  rc = dsr_batch_run(b);
+  if (!rc) rc = dsr_batch_download(b, mout.data());
+  if (!rc) {
+    for (int o = 0; o < n_obj; ++o) {            // the reference view's record, the counts summed
+      out[o] = mout[leader[o]];
+      for (int v = 1; v < views[o]; ++v) {
+        out[o].n_valid_last += mout[leader[o] + v].n_valid_last;
+        out[o].k_last += mout[leader[o] + v].k_last;
+      }
+    }
+    if (fail_view) {                             // (tie[] order is object order)
+      if (hipMemcpy(fail_view, b->fail_view, sizeof(int) * n_obj, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(ctx, "fail_view download failed");
+    }
+  }
+  if (!rc && trace) rc = trace_download(b, n_obj, leader.data(), trace);
+  if (!rc && stats) rc = dsr_batch_stats(b, stats);
   dsr_batch_destroy(b);
   return rc;
 }

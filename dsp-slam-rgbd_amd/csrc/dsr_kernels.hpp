@@ -2094,28 +2094,84 @@ __device__ inline float rotation_prior_fp32(const float* Tco, float* jrot) {
 }
 #endif
 
+// Several views of one object (dsr_reconstruct_views): every view is an ordinary batch member
+// (own ObjDesc / ObjState, own samples, tiles and red[] sums) and the members of one object are
+// consecutive, the reference view first (the leader).  k_views_pose derives the members' poses
+// from the leader's: T_v = T . C_v, C_v = inverse(t_view_ref_v) (rounded once on the host), in
+// mm4's fixed operation order — after k_init_state and after every solve, so the views never
+// move on their own.  tie[i] = (leader, members) of tied object i; st / cview are pre-offset
+// like tie's leaders (object groups).  One workgroup per tied object, one lane per view.
+__global__ void k_views_pose(const int2* __restrict__ tie, ObjState* st, const float* __restrict__ cview) {
+  const int2 t = tie[blockIdx.x];
+  for (int m = 1 + threadIdx.x; m < t.y; m += blockDim.x)
+    mm4(st[t.x].T, cview + (size_t)(t.x + m) * 16, st[t.x + m].T);
+}
+
+// solve_object: optimizer.py:131-194 for one object by one workgroup — the body of k_solve
+// (TIED = false: object o alone, nm = 1) and of k_solve_views (TIED = true: the object's nm views
+// are members o .. o + nm - 1, o the leader; their normal-equation sums are pooled, the one
+// solve updates the leader's pose and every member's code row).  The untied instantiation is
+// the arithmetic, statement for statement, of the kernel before the views existed.
 // trace_* hold [iteration][stride objects]; the pointers are pre-offset to this launch's
 // first object (object groups on concurrent streams, dsr_batch_run).
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDesc* __restrict__ desc,
-                                                         ObjState* st, float* __restrict__ zbuf,
-                                                         GNParams P, const float* __restrict__ red,
-                                                         float* __restrict__ trace_H,
-                                                         float* __restrict__ trace_v,
-                                                         int* __restrict__ trace_i, int stride) {
-  const int o = blockIdx.x;
+template <bool TIED>
+__device__ __forceinline__ void solve_object(const int o, const int nm, const ObjDesc* __restrict__ desc,
+                                             ObjState* st, float* __restrict__ zbuf, const GNParams& P,
+                                             const float* __restrict__ red, float* __restrict__ trace_H,
+                                             float* __restrict__ trace_v, int* __restrict__ trace_i,
+                                             int stride, int* __restrict__ fail_view) {
   ObjState& S = st[o];
-  if (S.status != ST_RUNNING) return;
   const int tid = threadIdx.x;
-  if (S.lite_viol > 0) {
-    // An audited sample's exact class differs from the lite pass's (dsr_mlp16.hpp): some
-    // unaudited sample may be misclassified too, so this iteration's terms are not trusted.
-    // Discard it — no update, no trace, no failure exit — and redo it with every sample
-    // decoded exactly (k_iter_begin); dsr_batch_run enqueues one spare iteration for this.
+  __shared__ int flag;
+  if constexpr (TIED) {
+    // The tie's state, decided by one lane: a failed view fails the object (every member gets
+    // the lowest failing view's reason, *fail_view its index); an audit violation in any view
+    // discards the iteration for all of them (k_solve's rule below), and the whole object
+    // decodes exactly from then on: a view left on the lite pass could discard a second
+    // iteration, for which no spare one is enqueued.
     if (tid == 0) {
-      S.lite_viol_total += S.lite_viol;
-      S.lite_redo = 1;
+      int stop = 0;
+      if (S.status == ST_DONE || *fail_view >= 0) {
+        stop = 1;
+      } else {
+        int fv = -1, viol = 0;
+        for (int m = nm - 1; m >= 0; --m) {
+          if (st[o + m].status == ST_FAIL) fv = m;
+          viol += st[o + m].lite_viol > 0 ? 1 : 0;
+        }
+        if (fv >= 0) {
+          const int reason = st[o + fv].fail_reason;
+          for (int m = 0; m < nm; ++m) {
+            st[o + m].status = ST_FAIL;
+            st[o + m].fail_reason = reason;
+          }
+          *fail_view = fv;
+          stop = 1;
+        } else if (viol) {
+          for (int m = 0; m < nm; ++m) {
+            st[o + m].lite_viol_total += st[o + m].lite_viol;
+            st[o + m].lite_redo = 1;
+          }
+          stop = 1;
+        }
+      }
+      flag = stop;
     }
-    return;
+    __syncthreads();
+    if (flag) return;           // (written again only after the next barrier)
+  } else {
+    if (S.status != ST_RUNNING) return;
+    if (S.lite_viol > 0) {
+      // An audited sample's exact class differs from the lite pass's (dsr_mlp16.hpp): some
+      // unaudited sample may be misclassified too, so this iteration's terms are not trusted.
+      // Discard it — no update, no trace, no failure exit — and redo it with every sample
+      // decoded exactly (k_iter_begin); dsr_batch_run enqueues one spare iteration for this.
+      if (tid == 0) {
+        S.lite_viol_total += S.lite_viol;
+        S.lite_redo = 1;
+      }
+      return;
+    }
   }
   const ObjDesc d = desc[o];
   __shared__ float Ss[SLOT_FLOATS];
@@ -2127,7 +2183,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDes
   __shared__ float scal[4];
   __shared__ int piv[NPAR];
   __shared__ float pivv[NPAR];
-  __shared__ int flag;
   constexpr int LP = NPAR + 3;                  // fp64 pitch 74: 16-byte aligned rows (the panel reads)
   __shared__ __attribute__((aligned(16))) double Lc[NPAR + 1][LP];   // Cholesky factor, b as row NPAR
   __shared__ double rdg[NPAR];                  // 1 / L[c][c]
@@ -2142,8 +2197,19 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDes
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
       const int e = min(tid + q * SOLVE_THREADS, SLOT_FLOATS - 1);
-      vs[q] = r[e];
-      vr[q] = r[SLOT_FLOATS + e];
+      if constexpr (TIED) {
+        // the views' sums pooled in view order: fp64, rounded once (one view: its own value)
+        double as = 0.0, ar = 0.0;
+        for (int m = 0; m < nm; ++m) {
+          as += (double)r[(size_t)m * SRED_STRIDE + e];
+          ar += (double)r[(size_t)m * SRED_STRIDE + SLOT_FLOATS + e];
+        }
+        vs[q] = (float)as;
+        vr[q] = (float)ar;
+      } else {
+        vs[q] = r[e];
+        vr[q] = r[SLOT_FLOATS + e];
+      }
     }
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
@@ -2167,7 +2233,13 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDes
   __syncthreads();
   const int it = S.iters_done;
   if (tid == 0) {
-    const float N = (float)d.n_pts, K = (float)S.k;
+    int Ni = d.n_pts, Ki = S.k;                         // (tied: N, K of the pooled sets)
+    if constexpr (TIED)
+      for (int m = 1; m < nm; ++m) {
+        Ni += desc[o + m].n_pts;
+        Ki += st[o + m].k;
+      }
+    const float N = (float)Ni, K = (float)Ki;
     const float sdf_loss = Ss[SLOT_FLOATS - 1] / N;
     const float ren_loss = Sr[SLOT_FLOATS - 1] / K;     // K == 0 -> NaN, like mean(empty)
     S.sdf_loss = sdf_loss;
@@ -2179,6 +2251,13 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDes
     if (f) {
       S.status = ST_FAIL;
       S.fail_reason = f;
+      if constexpr (TIED) {           // a failure of the pooled terms: no one view's, reported as view 0's
+        for (int m = 1; m < nm; ++m) {
+          st[o + m].status = ST_FAIL;
+          st[o + m].fail_reason = f;
+        }
+        *fail_view = 0;
+      }
     } else {
       scal[0] = P.k1 * ren_loss + P.k2 * sdf_loss;                 // :157
       scal[2] = N;
@@ -2526,7 +2605,12 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDes
   const long long tp3 = wall_clock64();
   if (tid == 0 && o == 0) printf("solve_prof %lld %lld %lld\n", tp1 - tp0, tp2 - tp1, tp3 - tp2);
 #endif
-  if (tid < CODE) zbuf[o * CODE + tid] = z[tid] + P.lr * dx[NPOSE + tid];   // :194
+  if (tid < CODE) {
+    const float zn = z[tid] + P.lr * dx[NPOSE + tid];             // :194
+    zbuf[o * CODE + tid] = zn;
+    if constexpr (TIED)
+      for (int m = 1; m < nm; ++m) zbuf[(o + m) * CODE + tid] = zn;
+  }
   if (tid == 0) {
     float xi[NPOSE], dT[16], Tn[16], Tprev[16];
     for (int i = 0; i < 16; ++i) Tprev[i] = S.T[i];
@@ -2537,6 +2621,15 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDes
     S.loss = scal[0];
     S.iters_done = it + 1;
     if (it + 1 >= P.iters) S.status = ST_DONE;
+    if constexpr (TIED)               // (the members' poses follow in k_views_pose)
+      for (int m = 1; m < nm; ++m) {
+        ObjState& V = st[o + m];
+        V.loss = scal[0];
+        V.sdf_loss = S.sdf_loss;
+        V.render_loss = S.render_loss;
+        V.iters_done = it + 1;
+        V.status = S.status;
+      }
     if (trace_v) {
       float* tv = trace_v + ((size_t)it * stride + o) * TRACE_V_STRIDE;
       for (int i = 0; i < NPAR; ++i) { tv[i] = bv[i]; tv[NPAR + i] = dx[i]; }
@@ -2548,11 +2641,43 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDes
     }
   }
   if (trace_i && tid == 0) {
-    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 0] = S.n_valid;
-    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 1] = S.k;
-    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 2] = S.n_eval;
-    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 3] = S.n_refine;
+    int c[4] = {S.n_valid, S.k, S.n_eval, S.n_refine};
+    if constexpr (TIED)               // the views' counts summed
+      for (int m = 1; m < nm; ++m) {
+        c[0] += st[o + m].n_valid;
+        c[1] += st[o + m].k;
+        c[2] += st[o + m].n_eval;
+        c[3] += st[o + m].n_refine;
+      }
+    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 0] = c[0];
+    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 1] = c[1];
+    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 2] = c[2];
+    trace_i[((size_t)it * stride + o) * TRACE_I_STRIDE + 3] = c[3];
   }
+}
+
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve(int n_obj, const ObjDesc* __restrict__ desc,
+                                                         ObjState* st, float* __restrict__ zbuf,
+                                                         GNParams P, const float* __restrict__ red,
+                                                         float* __restrict__ trace_H,
+                                                         float* __restrict__ trace_v,
+                                                         int* __restrict__ trace_i, int stride) {
+  solve_object<false>(blockIdx.x, 1, desc, st, zbuf, P, red, trace_H, trace_v, trace_i, stride, nullptr);
+}
+
+// k_solve_views: k_solve for tied batches, one workgroup per tied object (tie[] as in
+// k_views_pose; fail_view[i]: the view that failed object i, -1 while none has).  Every member's
+// red[] sums and state are complete when it runs: the members of an object share one stream.
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_views(const int2* __restrict__ tie,
+                                                               const ObjDesc* __restrict__ desc, ObjState* st,
+                                                               float* __restrict__ zbuf, GNParams P,
+                                                               const float* __restrict__ red,
+                                                               float* __restrict__ trace_H,
+                                                               float* __restrict__ trace_v,
+                                                               int* __restrict__ trace_i, int stride,
+                                                               int* __restrict__ fail_view) {
+  const int2 t = tie[blockIdx.x];
+  solve_object<true>(t.x, t.y, desc, st, zbuf, P, red, trace_H, trace_v, trace_i, stride, fail_view + blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------

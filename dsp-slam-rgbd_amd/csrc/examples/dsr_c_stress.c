@@ -96,6 +96,53 @@ static void no_device_paths(void) {
     int nv = 0, nf = 0;
     CHECK(dsr_mc_volume(NULL, v, 2, 0.f, NULL, 0, NULL, 0, &nv, &nf) < 0, "mc_volume(NULL ctx) accepted");
   }
+  {
+    /* dsr_reconstruct_views validates the views before it needs the device: no views, a scaled,
+       a sheared-last-row and a reflected t_view_ref, a reference view that is not the identity —
+       and, with every view valid, the missing context */
+    static const float pt[3] = {0.f, 0.f, 3.f};
+    static const float dep[1] = {3.f};
+    dsr_view_in vw[3];
+    memset(vw, 0, sizeof(vw));
+    for (int v = 0; v < 3; ++v) {
+      for (int i = 0; i < 4; ++i) vw[v].t_view_ref[i * 5] = 1.f;
+      vw[v].pts = pt; vw[v].n_pts = 1;
+      vw[v].rays = pt; vw[v].n_rays = 1;
+      vw[v].depth = dep; vw[v].n_depth = 1;
+    }
+    vw[1].t_view_ref[3] = 0.5f;                       /* a translation: still rigid */
+    vw[2].t_view_ref[0] = 0.f; vw[2].t_view_ref[2] = 1.f;      /* a quarter turn about y */
+    vw[2].t_view_ref[8] = -1.f; vw[2].t_view_ref[10] = 0.f;
+    dsr_views_object_in vin;
+    memset(&vin, 0, sizeof(vin));
+    for (int i = 0; i < 4; ++i) vin.t_cam_obj[i * 5] = 1.f;
+    vin.n_views = 3;
+    vin.views = vw;
+    dsr_object_out vout;
+    int fv = 7;
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, NULL, &vout, NULL, &fv, NULL) < 0, "views: NULL in accepted");
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, NULL, NULL, &fv, NULL) < 0, "views: NULL out accepted");
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 0, &vin, &vout, NULL, &fv, NULL) < 0, "views: n_obj 0 accepted");
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: NULL ctx accepted");
+    vin.n_views = 0;
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: n_views 0 accepted");
+    vin.n_views = 3;
+    vin.views = NULL;
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: NULL views accepted");
+    vin.views = vw;
+    for (int i = 0; i < 3; ++i) vw[1].t_view_ref[i * 5] = 1.1f;
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: scale 1.1 accepted");
+    for (int i = 0; i < 3; ++i) vw[1].t_view_ref[i * 5] = 1.f;
+    vw[1].t_view_ref[12] = 0.25f;
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: last row accepted");
+    vw[1].t_view_ref[12] = 0.f;
+    vw[1].t_view_ref[0] = -1.f;
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: reflection accepted");
+    vw[1].t_view_ref[0] = 1.f;
+    vw[0].t_view_ref[3] = 0.5f;
+    CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: moved view 0 accepted");
+    CHECK(fv == 7, "views: fail_view written by a rejected call");
+  }
   dsr_ctx* c = NULL;
   const int rc2 = dsr_ctx_create(-7, &c);
   CHECK(rc2 < 0 && c == NULL, "ctx_create(-7) = %d", rc2);

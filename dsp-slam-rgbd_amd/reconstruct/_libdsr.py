@@ -52,6 +52,18 @@ class ObjectIn(C.Structure):
                 ("code", FP), ("pose_is_obj_cam", C.c_int)]
 
 
+class ViewIn(C.Structure):
+    """dsr_view_in: one camera's observations of an object (dsr_reconstruct_views)."""
+    _fields_ = [("t_view_ref", C.c_float * 16), ("pts", FP), ("n_pts", C.c_int),
+                ("rays", FP), ("n_rays", C.c_int), ("depth", FP), ("n_depth", C.c_int)]
+
+
+class ViewsObjectIn(C.Structure):
+    """dsr_views_object_in: one object seen from n_views cameras, views[0] the reference view."""
+    _fields_ = [("t_cam_obj", C.c_float * 16), ("code", FP), ("pose_is_obj_cam", C.c_int),
+                ("n_views", C.c_int), ("views", C.POINTER(ViewIn))]
+
+
 class ObjectOut(C.Structure):
     _fields_ = [("t_cam_obj", C.c_float * 16), ("code", C.c_float * CODE_LEN),
                 ("loss", C.c_float), ("is_good", C.c_int), ("fail_reason", C.c_int),
@@ -131,6 +143,9 @@ SIGNATURES = {
     "dsr_reconstruct_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimParams), C.c_int,
                                         C.POINTER(ObjectIn), C.POINTER(ObjectOut),
                                         C.POINTER(Trace)]),
+    "dsr_reconstruct_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimParams), C.c_int,
+                                        C.POINTER(ViewsObjectIn), C.POINTER(ObjectOut),
+                                        C.POINTER(Trace), IP, C.POINTER(Stats)]),
     "dsr_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimParams), C.c_int,
                                    C.POINTER(ObjectIn), C.POINTER(C.c_void_p)]),
     "dsr_batch_run": (C.c_int, [C.c_void_p]),
@@ -165,6 +180,10 @@ SIGNATURES = {
     "dsr_mc_volume": (C.c_int, [C.c_void_p, FP, C.c_int, C.c_float, FP, C.c_int, IP, C.c_int, IP, IP]),
 }
 
+#: entry points added without an ABI number change: callers detect them by the symbol, so a
+#: library of the same ABI number built before them still loads (A/B runs under DSR_LIB)
+BY_SYMBOL = ("dsr_reconstruct_views",)
+
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it
 
@@ -185,6 +204,8 @@ def load_library(path: str | None = None):
                            "or __graft_entry__.build()); there is no CPU fallback")
         lib = C.CDLL(p)
         for name, (res, args) in SIGNATURES.items():
+            if name in BY_SYMBOL and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -12,6 +12,9 @@ runs in libdsr's HIP kernels on an MI355X (``include/dsr.h``):
   like the reference (optimizer.py:132-152).
 * ``Optimizer.reconstruct_objects([...])`` — NEW batched form: all objects of a
   keyframe / frame in one device pass.
+* ``Optimizer.reconstruct_objects_views([...])`` / ``reconstruct_object_views`` — NEW: one
+  code and one pose per object fitted to the pooled residuals of several keyframes' views
+  -> ``dsr_reconstruct_views``.
 * ``Optimizer.compute_sdf_loss_objectpoint_zhjd(pts_obj, code)`` —
   optimizer.py:207-213 -> ``dsr_sdf_eval``.
 * ``Optimizer.estimate_pose_cam_obj(...)`` — optimizer.py:46-87 -> ``dsr_pose_only``.
@@ -115,6 +118,24 @@ class Optimizer(object):
                                      is_good=True, loss=float(o.loss))
         return ForceKeyErrorDict(t_cam_obj=None, code=None, is_good=False, loss=float(o.loss))
 
+    def _trace_bufs(self, n):
+        """dsr_trace records for n objects and the numpy buffers they point into."""
+        it = max(1, self.num_iterations_joint_optim)
+        bufs = [dict(H=np.zeros((it, 71, 71), np.float32), b=np.zeros((it, 71), np.float32),
+                     dx=np.zeros((it, 71), np.float32), loss=np.zeros(it, np.float32),
+                     sdf_loss=np.zeros(it, np.float32), render_loss=np.zeros(it, np.float32),
+                     n_valid=np.zeros(it, np.int32), k=np.zeros(it, np.int32),
+                     t_obj_cam=np.zeros((it, 4, 4), np.float32),
+                     z=np.zeros((it, self.code_len), np.float32),
+                     n_decoded=np.zeros(it, np.int32), n_refined=np.zeros(it, np.int32)) for _ in range(n)]
+        tr = (L.Trace * n)()
+        for i, bb in enumerate(bufs):
+            tr[i] = L.Trace(*(L.fptr(bb[k]) for k in ("H", "b", "dx", "loss", "sdf_loss",
+                                                      "render_loss")),
+                            L.iptr(bb["n_valid"]), L.iptr(bb["k"]), L.fptr(bb["t_obj_cam"]),
+                            L.fptr(bb["z"]), L.iptr(bb["n_decoded"]), L.iptr(bb["n_refined"]))
+        return tr, bufs
+
     # ------------------------------------------------------------------ API
     def reconstruct_object(self, t_cam_obj, pts, rays, depth, code=None):
         """optimizer.py:90-205 (one object)."""
@@ -134,23 +155,7 @@ class Optimizer(object):
             c = ob[4] if len(ob) > 4 else None
             ins[i] = self._object_in(t, p, r, d, c, keep, pose_is_obj_cam)
         outs = (L.ObjectOut * n)()
-        tr = None
-        bufs = None
-        if trace:
-            it = max(1, self.num_iterations_joint_optim)
-            bufs = [dict(H=np.zeros((it, 71, 71), np.float32), b=np.zeros((it, 71), np.float32),
-                         dx=np.zeros((it, 71), np.float32), loss=np.zeros(it, np.float32),
-                         sdf_loss=np.zeros(it, np.float32), render_loss=np.zeros(it, np.float32),
-                         n_valid=np.zeros(it, np.int32), k=np.zeros(it, np.int32),
-                         t_obj_cam=np.zeros((it, 4, 4), np.float32),
-                         z=np.zeros((it, self.code_len), np.float32),
-                         n_decoded=np.zeros(it, np.int32), n_refined=np.zeros(it, np.int32)) for _ in range(n)]
-            tr = (L.Trace * n)()
-            for i, bb in enumerate(bufs):
-                tr[i] = L.Trace(*(L.fptr(bb[k]) for k in ("H", "b", "dx", "loss", "sdf_loss",
-                                                          "render_loss")),
-                                L.iptr(bb["n_valid"]), L.iptr(bb["k"]), L.fptr(bb["t_obj_cam"]),
-                                L.fptr(bb["z"]), L.iptr(bb["n_decoded"]), L.iptr(bb["n_refined"]))
+        tr, bufs = self._trace_bufs(n) if trace else (None, None)
         t0 = time.time()
         ctx = self._ctx
         ctx.check(ctx.lib.dsr_reconstruct_batch(ctx.handle, self.decoder.handle,
@@ -162,6 +167,69 @@ class Optimizer(object):
         for i in range(n):
             res[i]["iters_done"] = int(outs[i].iters_done)
             res[i]["fail_reason"] = L.FAIL_REASONS.get(int(outs[i].fail_reason), "?")
+        if trace:
+            return res, bufs
+        return res
+
+    def reconstruct_object_views(self, t_cam_obj, views, code=None):
+        """One object fitted jointly to several cameras' observations (``reconstruct_objects_views``
+        with one object)."""
+        return self.reconstruct_objects_views([(t_cam_obj, views, code)])[0]
+
+    def reconstruct_objects_views(self, objects, trace=False, pose_is_obj_cam=False):
+        """``reconstruct_objects`` with ONE code and ONE pose per object fitted to the pooled
+        residuals of several views (dsr_reconstruct_views, include/dsr.h): ``objects`` is a list of
+        ``(t_cam_obj, views, code_or_None)`` and ``views`` a list of ``(t_view_ref, pts, rays,
+        depth)`` — view 0 the reference view (``t_view_ref`` the identity; ``t_cam_obj`` and the
+        result pose are in its camera frame), view v with the rigid ``x_view = t_view_ref @ x_ref``
+        (``reconstruct.utils.views_from_world`` builds them from keyframe poses) and its own points,
+        rays and depths in its own camera frame.  Returns the result dicts of
+        ``reconstruct_objects`` plus ``fail_view`` (the view that failed the object, -1 if none)
+        and, with ``trace``, the per-object traces of the pooled normal equations.  The underlying
+        batch's statistics are left in ``last_stats``."""
+        n = len(objects)
+        if n == 0:
+            return ([], []) if trace else []
+        ctx = self._ctx
+        if not hasattr(ctx.lib, "dsr_reconstruct_views"):
+            raise L.DsrError("this libdsr build has no dsr_reconstruct_views")
+        keep = []
+        ins = (L.ViewsObjectIn * n)()
+        for i, ob in enumerate(objects):
+            t, views = ob[:2]
+            code = ob[2] if len(ob) > 2 else None
+            c = None if code is None else _code(code, self.code_len)
+            vs = (L.ViewIn * max(1, len(views)))()
+            for v, (t_view_ref, pts, rays, depth) in enumerate(views):
+                tv = np.asarray(t_view_ref, np.float64).reshape(4, 4).astype(np.float32)
+                pts, rays = _f32(pts, 3), _f32(rays, 3)
+                depth = np.ascontiguousarray(np.asarray(depth, np.float32).reshape(-1))
+                if depth.shape[0] > rays.shape[0]:
+                    raise ValueError("depth holds more values than there are rays")
+                keep.extend([pts, rays, depth])
+                vs[v].t_view_ref[:] = tv.reshape(-1).tolist()
+                vs[v].pts, vs[v].n_pts = L.fptr(pts), pts.shape[0]
+                vs[v].rays, vs[v].n_rays = L.fptr(rays), rays.shape[0]
+                vs[v].depth, vs[v].n_depth = L.fptr(depth), depth.shape[0]
+            keep.extend([vs, c])
+            ins[i].t_cam_obj[:] = _f32(t).reshape(-1).tolist()
+            ins[i].code = L.fptr(c)
+            ins[i].pose_is_obj_cam = 1 if pose_is_obj_cam else 0
+            ins[i].n_views = len(views)
+            ins[i].views = vs
+        outs = (L.ObjectOut * n)()
+        tr, bufs = self._trace_bufs(n) if trace else (None, None)
+        fail_view = np.full(n, -1, np.int32)
+        st = L.Stats()
+        ctx.check(ctx.lib.dsr_reconstruct_views(ctx.handle, self.decoder.handle, C.byref(self.params), n, ins,
+                                                outs, tr, L.iptr(fail_view), C.byref(st)),
+                  "dsr_reconstruct_views")
+        self.last_stats = st
+        res = [self._result(outs[i], self.code_len) for i in range(n)]
+        for i in range(n):
+            res[i]["iters_done"] = int(outs[i].iters_done)
+            res[i]["fail_reason"] = L.FAIL_REASONS.get(int(outs[i].fail_reason), "?")
+            res[i]["fail_view"] = int(fail_view[i])
         if trace:
             return res, bufs
         return res

@@ -103,6 +103,20 @@ def get_decoder(configs, device=None):
     return config_decoder(configs.DeepSDF_DIR, device=device)
 
 
+def views_from_world(t_cam_world_list):
+    """The ``t_view_ref`` of ``Optimizer.reconstruct_objects_views`` from what a SLAM caller holds
+    per keyframe: world -> camera poses ``T_cv_w`` (SE(3), 4x4).  Keyframe 0 is the reference
+    view; ``t_view_ref_v = T_cv_w @ inverse(T_c0_w)`` in float64 (the identity, exactly, for
+    v = 0).  No reference counterpart (the reference fits one camera at a time)."""
+    ts = [np.asarray(t, np.float64).reshape(4, 4) for t in t_cam_world_list]
+    if not ts:
+        return []
+    inv0 = np.eye(4)
+    inv0[:3, :3] = ts[0][:3, :3].T
+    inv0[:3, 3] = -ts[0][:3, :3].T @ ts[0][:3, 3]
+    return [np.eye(4)] + [t @ inv0 for t in ts[1:]]
+
+
 def create_voxel_grid(vol_dim=128):
     """utils.py:97-116.  Note the reference's ``LongTensor / vol_dim`` is TRUE division
     in torch >= 1.6 (fp32), so its x/y columns are not integer lattice indices; this

@@ -316,6 +316,52 @@ def make_object(seed: int, n_pts: int = 2048, n_bg: int = 200, scale: float = 2.
     )
 
 
+@dataclass
+class SyntheticObjectViews:
+    t_cam_obj: np.ndarray   # (4,4) f32 initial object->reference-camera Sim(3)
+    views: list             # [(t_view_ref (4,4) f64, pts (N_v,3) f32, rays (N_v+n_bg,3) f32, depth (N_v,) f32)]
+    t_true: np.ndarray      # (4,4) f32 the true object->reference-camera pose
+
+
+def make_object_views(seed: int, n_views: int = 3, n_pts: int = 2048, n_bg: int = 200,
+                      scale: float = 2.0, tz: float = 15.0, upright: bool = True,
+                      perturb: float = 1.0, radius: float = 0.5) -> SyntheticObjectViews:
+    """One object seen from ``n_views`` cameras (Optimizer.reconstruct_objects_views).
+
+    View 0 is :func:`make_object`'s camera, observations and perturbed start pose, unchanged.
+    Camera v >= 1 is camera 0 rotated about the camera-y axis through the true object centre by
+    +-U(0.5, 2.5) rad (sign alternating with v) and shifted by U(+-0.05 tz) per axis, so y stays
+    the gravity axis of every view.  View v observes ``n_pts + 13 v`` fresh sphere points drawn as
+    make_object draws them, foreground rays pts / z, and ``n_bg`` background rays
+    U(+-0.6 scale / mean z) around the projected object centre.  The views draw from a stream of
+    their own, so view 0 does not depend on ``n_views``."""
+    ob = make_object(seed, n_pts, n_bg, scale, tz, upright, perturb, radius)
+    views = [(np.eye(4), ob.pts, ob.rays, ob.depth)]
+    rng = np.random.default_rng([seed, 0x76696577])
+    T = ob.t_true.astype(np.float64)
+    c = T[:3, 3]
+    for v in range(1, n_views):
+        ang = rng.uniform(0.5, 2.5) * (1.0 if v % 2 else -1.0)
+        dt = rng.uniform(-0.05 * tz, 0.05 * tz, size=3)
+        Rv = _rot_y(ang)
+        tvr = np.eye(4)
+        tvr[:3, :3] = Rv
+        tvr[:3, 3] = c - Rv @ c + dt
+        Tv = tvr @ T                                   # object -> camera v
+        n = n_pts + 13 * v
+        p = rng.standard_normal((n, 3))
+        p = radius * p / np.linalg.norm(p, axis=1, keepdims=True)
+        pts = p @ Tv[:3, :3].T + Tv[:3, 3]
+        fg = pts / pts[:, 2:3]
+        span = 0.6 * scale / pts[:, 2].mean()
+        u0, v0 = Tv[0, 3] / Tv[2, 3], Tv[1, 3] / Tv[2, 3]
+        bg = np.stack([u0 + rng.uniform(-span, span, n_bg), v0 + rng.uniform(-span, span, n_bg),
+                       np.ones(n_bg)], axis=1)
+        views.append((tvr, pts.astype(np.float32), np.concatenate([fg, bg], axis=0).astype(np.float32),
+                      pts[:, 2].astype(np.float32)))
+    return SyntheticObjectViews(t_cam_obj=ob.t_cam_obj, views=views, t_true=ob.t_true)
+
+
 def kitti_object(obj_id: int, base_seed: int = 1000, n_pts: int = 2048):
     """Metric-unit object (config 2): KITTI params, 2048 pts, 2048+200 rays, s=2, tz=15."""
     return make_object(base_seed + obj_id, n_pts=n_pts, scale=2.0, tz=15.0, upright=True)

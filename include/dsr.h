@@ -236,6 +236,60 @@ int dsr_reconstruct_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_
                           int n_obj, const dsr_object_in* in, dsr_object_out* out,
                           const dsr_trace* trace);
 
+/* ---- joint shape + pose GN over several views of one object: Optimizer.reconstruct_object
+ * (optimizer.py:90-205) with the residuals of V >= 1 cameras pooled into ONE code and ONE pose
+ * (no reference counterpart as a call: the mono caller re-runs the single-view fit every 5
+ * keyframes with a warm start, LocalMapping_util.cc:284-295, :394; callers detect this entry
+ * point by its symbol, the ABI number is unchanged).
+ * View 0 is the reference view: t_cam_obj, the result pose and the upright prior (loss.py:169-192)
+ * are in its camera frame and its t_view_ref must be the identity.  View v sees
+ * x_view = t_view_ref . x_ref (rigid) and brings its own pts / rays / depth in ITS camera frame,
+ * laid out as in dsr_object_in (pts may be empty).  Per iteration, with T = t_obj_ref and
+ * C_v = inverse(t_view_ref_v) (fp64 on the host, rounded once): every view's depth range,
+ * samples (optimizer.py:122-128), SDF and render residuals and Jacobians (loss.py:22-43,
+ * :60-166) are taken under T_v = T . C_v (T_0 = T itself); the reference updates
+ * t_obj_cam <- exp(dx) t_obj_cam (optimizer.py:192) and differentiates at object-frame points
+ * (loss.py:38, :162), so all views' rows are derivatives with respect to the same 71 parameters
+ * and J_sdf / r_sdf (N = sum N_v) and J_render / r_render (K = sum K_v) are their
+ * concatenations; Huber weights, the means, the loss, the priors, the damping and the solve
+ * (optimizer.py:157-194) are applied to the pooled sets unchanged, the rotation prior once, at T.
+ * T <- exp_sim3(lr dx[:7]) T, z <- z + lr dx[7:], and every T_v is re-derived from the new T.
+ * Numeric failures are the reference's, per object: a view with < 10 in-ball samples
+ * (DSR_FAIL_RENDER_FEW, the lowest such view in fail_view), N == 0 over all views
+ * (DSR_FAIL_SDF_NAN), K == 0 over all views (DSR_FAIL_RENDER_NAN; failures of the pooled terms
+ * are reported as view 0's); one view without points or without render points is fine.
+ * With n_views == 1 everywhere the results are bitwise those of dsr_reconstruct_batch.
+ * out[i] is the reference view's record with n_valid_last / k_last summed over the views;
+ * trace (NULL or n_obj records) holds the pooled H, b, dx and losses, the summed counts and the
+ * reference view's t_obj_cam and z; fail_view (NULL or n_obj ints) the view that failed each
+ * object, -1 if none; stats (NULL or one record) the statistics of the underlying batch, whose
+ * members are the views.  Errors (not numeric failures): n_views < 1, a t_view_ref that is not
+ * rigid (last row not 0 0 0 1, R^T R - I beyond 1e-4, a reflection), and every input
+ * dsr_batch_create rejects. */
+typedef struct {
+  float t_view_ref[16];           /* rigid reference-camera -> this camera, row-major */
+  const float* pts;               /* (n_pts,3) surface points, this view's camera frame */
+  int n_pts;
+  const float* rays;              /* (n_rays,3) ray directions, fg rays first */
+  int n_rays;
+  const float* depth;             /* (n_depth,) observed depth of the fg rays */
+  int n_depth;
+} dsr_view_in;
+
+typedef struct {
+  float t_cam_obj[16];            /* initial object->reference-camera Sim(3), row-major */
+  const float* code;              /* (code_len,) warm-start code or NULL (=zeros) */
+  int pose_is_obj_cam;            /* 1: t_cam_obj[] already holds t_obj_cam (teacher forcing) */
+  int n_views;                    /* V >= 1 */
+  const dsr_view_in* views;       /* views[0]: the reference view */
+} dsr_views_object_in;
+
+int dsr_reconstruct_views(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p, int n_obj,
+                          const dsr_views_object_in* in, dsr_object_out* out,
+                          const dsr_trace* trace,   /* NULL or n_obj records */
+                          int* fail_view,           /* NULL or n_obj: failing view, -1 if none */
+                          dsr_stats* stats);        /* NULL or the underlying batch's stats */
+
 /* Resident batches for benchmarking / streaming (inputs uploaded once; a run
  * re-initializes the optimizer state on device and executes all iterations on
  * the context stream). */
