@@ -23,6 +23,7 @@
 #include "dsr_kernels.hpp"
 #include "dsr_mc.hpp"
 #include "dsr_mesh.hpp"
+#include "dsr_render.hpp"
 
 #ifndef DSR_DEFAULT_FWD_VARIANT
 #define DSR_DEFAULT_FWD_VARIANT 12  // split-fp16 (3xFP16) + s_setprio (A/B: tools/fwd_variants.py)
@@ -3057,6 +3058,413 @@ int dsr_mesher_peek(dsr_mesher* m, int slot, float* lite_vol, float* final_vol, 
   if (lite_vol) DSR_CHECK(ctx, hipMemcpy(lite_vol, b->lite + o, sizeof(float) * m->n, hipMemcpyDeviceToHost));
   if (final_vol) DSR_CHECK(ctx, hipMemcpy(final_vol, b->vol + o, sizeof(float) * m->n, hipMemcpyDeviceToHost));
   if (tile_flags) DSR_CHECK(ctx, hipMemcpy(tile_flags, b->tflag + (size_t)slot * m->nt, m->nt, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- sphere-traced images (kernels: dsr_render.hpp) ---------------------------
+constexpr int RENDER_PASS_OBJ = 64;   // objects per pass at most (bounds the tile padding)
+
+struct dsr_renderer {
+  dsr_ctx* ctx = nullptr;
+  const dsr_decoder* dec = nullptr;
+  dsr_camera cam{};
+  int npix = 0, cap = 0;             // W*H; ray slots (2*W*H)
+  int max_chunks = 0, max_tiles = 0; // of one pass
+  std::vector<void*> allocs;
+  float *lam = nullptr, *lam0 = nullptr, *lam1 = nullptr, *dense = nullptr;
+  int* state = nullptr;
+  float4* cand = nullptr;            // cap + 64 * RENDER_PASS_OBJ (the normal pass pads tiles per object)
+  int *ccnt = nullptr, *gpos = nullptr, *ntiles = nullptr;
+  Tile* tiles = nullptr;
+  unsigned long long* keys = nullptr;
+  float *depth = nullptr, *normals = nullptr, *raw = nullptr;   // normals / raw: on the first normals call
+  int* inst = nullptr;
+  RenderStepStats* ss = nullptr;
+  // per-call arrays, grown on demand
+  int obj_cap = 0, chunk_cap = 0;
+  RenderObj* objs = nullptr;
+  ObjDesc* desc = nullptr;
+  float *codes = nullptr, *b0 = nullptr, *b4 = nullptr;
+  int *olive = nullptr, *otile = nullptr, *counters = nullptr;
+  RayChunk* chunks = nullptr;
+  hipEvent_t ev[4] = {};
+  dsr_render_stats st{};
+};
+
+static bool renderer_alloc(dsr_renderer* r, void** p, size_t bytes) {
+  if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  r->allocs.push_back(*p);
+  return true;
+}
+static void renderer_release(dsr_renderer* r, void* p) {
+  if (!p) return;
+  hipFree(p);
+  r->allocs.erase(std::remove(r->allocs.begin(), r->allocs.end(), p), r->allocs.end());
+}
+
+// One object's pose for the tracer: T_oc = inverse(t_cam_obj) in fp64, rounded once, the ball's
+// centre and radius (s = det(R_co)^(1/3)).  false: last row not 0 0 0 1, or det <= 0.
+struct RenderPose {
+  float Toc[12];
+  double c[3], rho;
+};
+static bool render_pose(const float* t, RenderPose* P) {
+  if (t[12] != 0.f || t[13] != 0.f || t[14] != 0.f || t[15] != 1.f) return false;
+  double m[9], t3[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) m[i * 3 + j] = t[i * 4 + j];
+    t3[i] = t[i * 4 + 3];
+  }
+  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+  if (!(det > 0.0) || !std::isfinite(det)) return false;
+  const double inv[9] = {c00 / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
+                         c01 / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
+                         c02 / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) P->Toc[i * 4 + j] = (float)inv[i * 3 + j];
+    P->Toc[i * 4 + 3] = (float)(-(inv[i * 3] * t3[0] + inv[i * 3 + 1] * t3[1] + inv[i * 3 + 2] * t3[2]));
+    P->c[i] = t3[i];
+  }
+  P->rho = std::cbrt(det);
+  return true;
+}
+
+// The rectangle rule (include/dsr.h: dsr_render_layout): rect = u_min, v_min, u_max, v_max.
+static int render_rect(const dsr_camera* cam, double near, const RenderPose& P, int* rect) {
+  rect[0] = rect[1] = 0;
+  rect[2] = rect[3] = -1;
+  const double z0 = P.c[2] - P.rho, z1 = P.c[2] + P.rho;
+  if (!(z0 >= near)) return DSR_RENDER_SKIP_NEAR;
+  const double f[2] = {cam->fx, cam->fy}, pp[2] = {cam->cx, cam->cy};
+  const int size[2] = {cam->width, cam->height};
+  int lo[2], hi[2];
+  for (int a = 0; a < 2; ++a) {
+    const double x0 = P.c[a] - P.rho, x1 = P.c[a] + P.rho;
+    const double q[4] = {x0 / z0, x0 / z1, x1 / z0, x1 / z1};
+    const double mn = std::min(std::min(q[0], q[1]), std::min(q[2], q[3]));
+    const double mx = std::max(std::max(q[0], q[1]), std::max(q[2], q[3]));
+    const double l = std::floor(pp[a] + f[a] * mn), h = std::ceil(pp[a] + f[a] * mx);
+    if (!(l <= size[a] - 1) || !(h >= 0)) return DSR_RENDER_OFFSCREEN;
+    lo[a] = (int)std::max(l, 0.0);
+    hi[a] = (int)std::min(h, (double)(size[a] - 1));
+  }
+  rect[0] = lo[0];
+  rect[1] = lo[1];
+  rect[2] = hi[0];
+  rect[3] = hi[1];
+  return DSR_RENDER_OK;
+}
+
+static const char* camera_error(const dsr_camera* cam) {
+  if (cam->width <= 0 || cam->height <= 0) return "image size must be positive";
+  if (!(cam->fx > 0.f) || !(cam->fy > 0.f)) return "focal lengths must be positive";
+  if ((long long)cam->width * cam->height > (1 << 24)) return "image larger than 2^24 pixels";
+  return nullptr;
+}
+
+int dsr_render_layout(const dsr_camera* cam, float near, int n_obj, const dsr_render_object* objs, int* rect,
+                      int* status) {
+  if (!cam || n_obj < 0 || (n_obj > 0 && (!objs || !rect || !status))) return -2;
+  if (camera_error(cam)) return -2;
+  const double nr = near > 0.f ? near : 0.01f;
+  for (int i = 0; i < n_obj; ++i) {
+    RenderPose P;
+    if (!render_pose(objs[i].t_cam_obj, &P)) return -2;
+    status[i] = render_rect(cam, nr, P, rect + 4 * i);
+  }
+  return 0;
+}
+
+int dsr_renderer_destroy(dsr_renderer* r) {
+  if (!r) return 0;
+  hipSetDevice(r->ctx->device);
+  hipStreamSynchronize(r->ctx->stream);
+  for (hipEvent_t e : r->ev)
+    if (e) hipEventDestroy(e);
+  for (void* p : r->allocs) hipFree(p);
+  delete r;
+  return 0;
+}
+
+int dsr_renderer_create(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_camera* cam, dsr_renderer** out) {
+  if (!ctx || !dec || !cam || !out) return fail(ctx, "null argument");
+  *out = nullptr;
+  if (const char* e = camera_error(cam)) return fail(ctx, e);
+  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  hipSetDevice(ctx->device);
+  auto* r = new dsr_renderer();
+  r->ctx = ctx;
+  r->dec = dec;
+  r->cam = *cam;
+  r->npix = cam->width * cam->height;
+  r->cap = 2 * r->npix;
+  r->max_chunks = r->cap / RCHUNK + RENDER_PASS_OBJ;
+  r->max_tiles = r->cap / TILE + RENDER_PASS_OBJ;
+  const size_t cap = (size_t)r->cap;
+  auto A = [&](void** p, size_t bytes) { return renderer_alloc(r, p, bytes); };
+  bool ok = A((void**)&r->lam, sizeof(float) * cap) && A((void**)&r->lam0, sizeof(float) * cap) &&
+            A((void**)&r->lam1, sizeof(float) * cap) && A((void**)&r->dense, sizeof(float) * cap) &&
+            A((void**)&r->state, sizeof(int) * cap) &&
+            A((void**)&r->cand, sizeof(float4) * (cap + (size_t)TILE * RENDER_PASS_OBJ)) &&
+            A((void**)&r->ccnt, sizeof(int) * r->max_chunks) && A((void**)&r->gpos, sizeof(int) * r->max_chunks) &&
+            A((void**)&r->ntiles, sizeof(int)) && A((void**)&r->tiles, sizeof(Tile) * r->max_tiles) &&
+            A((void**)&r->keys, sizeof(unsigned long long) * r->npix) &&
+            A((void**)&r->depth, sizeof(float) * r->npix) && A((void**)&r->inst, sizeof(int) * r->npix) &&
+            A((void**)&r->ss, sizeof(RenderStepStats));
+  for (hipEvent_t& e : r->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    dsr_renderer_destroy(r);
+    return fail(ctx, "hipMalloc failed (renderer)");
+  }
+  *out = r;
+  return 0;
+}
+
+int dsr_renderer_stats_get(const dsr_renderer* r, dsr_render_stats* st) {
+  if (!r || !st) return -2;
+  *st = r->st;
+  return 0;
+}
+
+// objects per pass: RENDER_PASS_OBJ, or DSR_RENDER_PASS_OBJ (1..64) under DSR_TEST_HOOKS=1
+static int render_pass_obj() {
+  const char* e = hook_env("DSR_RENDER_PASS_OBJ");
+  const int v = e ? atoi(e) : RENDER_PASS_OBJ;
+  return v >= 1 && v <= RENDER_PASS_OBJ ? v : RENDER_PASS_OBJ;
+}
+
+int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_obj, const dsr_render_object* in,
+                        float* depth, int* instance, float* normals, dsr_render_object_out* per_obj) {
+  if (!r) return -2;
+  dsr_ctx* ctx = r->ctx;
+  if (!params || !depth || !instance || (n_obj > 0 && !in)) return fail(ctx, "null argument");
+  if (n_obj < 0) return fail(ctx, "n_obj must be >= 0");
+  const float hit_eps = params->hit_eps == 0.f ? 1e-4f : params->hit_eps;
+  const int max_steps = params->max_steps == 0 ? 48 : params->max_steps;
+  const float damp = params->damp == 0.f ? 1.f : params->damp;
+  const float near = params->near == 0.f ? 0.01f : params->near;
+  if (!(hit_eps > 0.f)) return fail(ctx, "hit_eps must be > 0");
+  if (max_steps < 1 || max_steps > 256) return fail(ctx, "max_steps must be in [1, 256]");
+  if (!(near > 0.f)) return fail(ctx, "near must be > 0");
+  if (!std::isfinite(damp)) return fail(ctx, "damp must be finite");
+  const bool want_n = params->normals != 0;
+  if (want_n && !normals) return fail(ctx, "null argument (normals requested)");
+  for (int i = 0; i < n_obj; ++i)
+    if (!in[i].code) return fail(ctx, "null argument (code)");
+  if (!variant_kernels_ok(r->dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  const dsr_decoder* dec = r->dec;
+  const DevDecoder& D = dec->D;
+  const RenderCam C{r->cam.fx, r->cam.fy, r->cam.cx, r->cam.cy, r->cam.width, r->cam.height};
+  const int npix = r->npix;
+
+  // ---- host layout: poses, rectangles, passes, chunks
+  std::vector<RenderObj> ho(n_obj);
+  std::vector<ObjDesc> hd(n_obj);
+  std::vector<int> status(n_obj), rects((size_t)4 * n_obj);
+  std::vector<float> hz((size_t)n_obj * CODE, 0.f);
+  std::vector<RayChunk> hc;
+  struct Pass { int obj0, n_obj, chunk0, n_chunk, n_tiles_max; };
+  std::vector<Pass> passes;
+  const int pass_obj = render_pass_obj();
+  {
+    Pass cur{0, 0, 0, 0, 0};
+    int used = 0;
+    for (int i = 0; i < n_obj; ++i) {
+      RenderPose P;
+      if (!render_pose(in[i].t_cam_obj, &P))
+        return fail(ctx, "t_cam_obj must have the last row 0 0 0 1 and a positive determinant (object " + std::to_string(i) + ")");
+      int* rc = &rects[(size_t)4 * i];
+      status[i] = render_rect(&r->cam, near, P, rc);
+      RenderObj& o = ho[i];
+      std::memcpy(o.Toc, P.Toc, sizeof(o.Toc));
+      o.u0 = rc[0];
+      o.v0 = rc[1];
+      o.w = rc[2] - rc[0] + 1;
+      o.h = rc[3] - rc[1] + 1;
+      const int area = o.w * o.h;                     // 0 for skipped / off-screen objects; <= W*H
+      if (cur.n_obj > 0 && (used + area > r->cap || cur.n_obj >= pass_obj)) {
+        passes.push_back(cur);
+        cur = Pass{i, 0, (int)hc.size(), 0, 0};
+        used = 0;
+      }
+      o.ray_off = used;
+      o.chunk0 = (int)hc.size();
+      o.nchunk = (area + RCHUNK - 1) / RCHUNK;
+      o.pad = 0;
+      for (int c = 0; c < o.nchunk; ++c) hc.push_back(RayChunk{i, c * RCHUNK});
+      hd[i] = ObjDesc{};
+      hd[i].cand_off = used;
+      hd[i].ray_off = used;
+      hd[i].n_rays = area;
+      used += area;
+      cur.n_obj += 1;
+      cur.n_chunk += o.nchunk;
+      cur.n_tiles_max += (area + TILE - 1) / TILE;
+      std::memcpy(&hz[(size_t)i * CODE], in[i].code, sizeof(float) * dec->code_len);   // a 32-D code: zero-padded
+    }
+    if (cur.n_obj > 0) passes.push_back(cur);
+  }
+  const int n_chunk = (int)hc.size();
+
+  hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  // the uploads below read the host vectors above asynchronously: no return, an error's
+  // included, leaves this frame before the stream has drained
+  struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{s};
+  float* lnw = nullptr;          // LayerNorm decoders: the context stream's Jacobian workspace
+  if (want_n && D.ln_mask && !(lnw = ln_workspace(ctx, 0))) return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
+  // ---- per-call device arrays
+  if (n_obj > r->obj_cap) {
+    for (void* p : {(void*)r->objs, (void*)r->desc, (void*)r->codes, (void*)r->b0, (void*)r->b4, (void*)r->olive,
+                    (void*)r->otile, (void*)r->counters})
+      renderer_release(r, p);
+    r->objs = nullptr; r->desc = nullptr; r->codes = r->b0 = r->b4 = nullptr; r->olive = r->otile = r->counters = nullptr;
+    r->obj_cap = 0;
+    const size_t n = (size_t)std::max(n_obj, 16);
+    auto A = [&](void** p, size_t bytes) { return renderer_alloc(r, p, bytes); };
+    if (!A((void**)&r->objs, sizeof(RenderObj) * n) || !A((void**)&r->desc, sizeof(ObjDesc) * n) ||
+        !A((void**)&r->codes, sizeof(float) * CODE * n) || !A((void**)&r->b0, sizeof(float) * HID * n) ||
+        !A((void**)&r->b4, sizeof(float) * HID * n) || !A((void**)&r->olive, sizeof(int) * n) ||
+        !A((void**)&r->otile, sizeof(int) * n) || !A((void**)&r->counters, sizeof(int) * RC_INTS * n))
+      return fail(ctx, "hipMalloc failed (render objects)");
+    r->obj_cap = (int)n;
+  }
+  if (n_chunk > r->chunk_cap) {
+    renderer_release(r, r->chunks);
+    r->chunks = nullptr;
+    r->chunk_cap = 0;
+    const size_t n = (size_t)std::max(n_chunk, 64);
+    if (!renderer_alloc(r, (void**)&r->chunks, sizeof(RayChunk) * n)) return fail(ctx, "hipMalloc failed (render chunks)");
+    r->chunk_cap = (int)n;
+  }
+  if (want_n && !r->raw) {
+    const size_t np = (size_t)npix + (size_t)TILE * RENDER_PASS_OBJ;
+    if (!renderer_alloc(r, (void**)&r->normals, sizeof(float) * 3 * npix) ||
+        !renderer_alloc(r, (void**)&r->raw, sizeof(float) * (IN + 1) * np)) {
+      r->raw = nullptr;
+      return fail(ctx, "hipMalloc failed (render normals)");
+    }
+  }
+  DSR_CHECK(ctx, hipMemsetAsync(r->keys, 0xff, sizeof(unsigned long long) * npix, s));
+  DSR_CHECK(ctx, hipMemsetAsync(r->ss, 0, sizeof(RenderStepStats), s));
+  if (n_obj > 0) {
+    DSR_CHECK(ctx, hipMemcpyAsync(r->objs, ho.data(), sizeof(RenderObj) * n_obj, hipMemcpyHostToDevice, s));
+    DSR_CHECK(ctx, hipMemcpyAsync(r->desc, hd.data(), sizeof(ObjDesc) * n_obj, hipMemcpyHostToDevice, s));
+    DSR_CHECK(ctx, hipMemcpyAsync(r->codes, hz.data(), sizeof(float) * CODE * n_obj, hipMemcpyHostToDevice, s));
+    DSR_CHECK(ctx, hipMemsetAsync(r->counters, 0, sizeof(int) * RC_INTS * n_obj, s));
+    if (n_chunk > 0)
+      DSR_CHECK(ctx, hipMemcpyAsync(r->chunks, hc.data(), sizeof(RayChunk) * n_chunk, hipMemcpyHostToDevice, s));
+    for (int i = 0; i < n_obj; ++i)
+      hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, (const float*)r->codes + (size_t)i * CODE,
+                         r->b0 + (size_t)i * HID, r->b4 + (size_t)i * HID);
+  }
+  dsr_render_stats st{};
+  st.n_obj = n_obj;
+  const FwdKernel fwdk = fwd_kernel_for(D, query_fwd_variant());
+  const ErtArgs EX{nullptr, 1, 0.f, nullptr, nullptr};
+  const MaskArgs MX{nullptr, nullptr, nullptr, nullptr};
+  // ---- the march, pass by pass: everything enqueued, one synchronisation per pass
+  for (const Pass& p : passes) {
+    if (p.n_chunk == 0) continue;                       // only objects without rays
+    st.n_passes += 1;
+    const RayChunk* ch = r->chunks + p.chunk0;
+    const int grid = std::max(1, std::min(ctx->n_cu, p.n_tiles_max));
+    DSR_CHECK(ctx, hipEventRecord(r->ev[0], s));
+    hipLaunchKernelGGL(k_rt_setup, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch, r->lam,
+                       r->lam0, r->lam1, r->state, r->ccnt);
+    DSR_CHECK(ctx, hipEventRecord(r->ev[1], s));
+    for (int k = 0; k < max_steps; ++k) {
+      hipLaunchKernelGGL(k_rt_scan, dim3(1), dim3(RT_SCAN_THREADS), 0, s, p.n_chunk, p.chunk0, p.obj0, p.n_obj,
+                         (const RenderObj*)r->objs, (const int*)r->ccnt, r->gpos, r->olive, r->otile, r->ntiles, k,
+                         r->ss, r->counters);
+      hipLaunchKernelGGL(k_rt_emit, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch, p.chunk0,
+                         (const int*)r->gpos, (const int*)r->olive, (const int*)r->otile, (const int*)r->state,
+                         (const float*)r->lam, r->cand, r->tiles, 0);
+      hipLaunchKernelGGL(fwdk, dim3(grid), dim3(512), 0, s, D, (const Tile*)r->tiles, (const int*)r->ntiles,
+                         (const ObjDesc*)r->desc, (const float4*)r->cand, (const float*)r->b0, (const float*)r->b4,
+                         r->dense, (unsigned*)nullptr, EX, MX);
+      hipLaunchKernelGGL(k_rt_advance, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch,
+                         (const float*)r->dense, r->lam, (const float*)r->lam0, (const float*)r->lam1, r->state,
+                         r->keys, r->counters, r->ccnt, RenderMarch{hit_eps, damp, k == max_steps - 1});
+    }
+    DSR_CHECK(ctx, hipEventRecord(r->ev[2], s));
+    DSR_CHECK(ctx, hipGetLastError());
+    DSR_CHECK(ctx, hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, r->ev[0], r->ev[1]) == hipSuccess) st.setup_ms += ms;
+    if (hipEventElapsedTime(&ms, r->ev[1], r->ev[2]) == hipSuccess) st.march_ms += ms;
+  }
+  // ---- resolve, n_visible, normals
+  DSR_CHECK(ctx, hipEventRecord(r->ev[0], s));
+  hipLaunchKernelGGL(k_rt_resolve, dim3((npix + 255) / 256), dim3(256), 0, s, (const unsigned long long*)r->keys, npix,
+                     r->depth, r->inst);
+  if (n_chunk > 0)
+    hipLaunchKernelGGL(k_rt_visible, dim3(n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs,
+                       (const RayChunk*)r->chunks, (const int*)r->inst, r->counters);
+  if (want_n) {
+    DSR_CHECK(ctx, hipMemsetAsync(r->normals, 0, sizeof(float) * 3 * npix, s));
+    const JacKernel jack = jac_kernel_for(D);
+    GNParams GP{};
+    for (const Pass& p : passes) {
+      if (p.n_chunk == 0) continue;
+      const RayChunk* ch = r->chunks + p.chunk0;
+      const int grid = std::max(1, std::min(ctx->n_cu, p.n_tiles_max));
+      hipLaunchKernelGGL(k_rt_winners, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch,
+                         (const unsigned long long*)r->keys, r->lam, r->state, r->ccnt);
+      hipLaunchKernelGGL(k_rt_scan, dim3(1), dim3(RT_SCAN_THREADS), 0, s, p.n_chunk, p.chunk0, p.obj0, p.n_obj,
+                         (const RenderObj*)r->objs, (const int*)r->ccnt, r->gpos, r->olive, r->otile, r->ntiles, -1,
+                         r->ss, r->counters);
+      hipLaunchKernelGGL(k_rt_emit, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch, p.chunk0,
+                         (const int*)r->gpos, (const int*)r->olive, (const int*)r->otile, (const int*)r->state,
+                         (const float*)r->lam, r->cand, r->tiles, 1);
+      hipLaunchKernelGGL(jack, dim3(grid), dim3(512), 0, s, D, (const Tile*)r->tiles, (const int*)r->ntiles,
+                         (const ObjDesc*)r->desc, (const ObjState*)nullptr, (const float*)nullptr,
+                         (const float4*)nullptr, (const float*)nullptr, (const float*)r->b0, (const float*)r->b4, GP,
+                         (float*)nullptr, (const float4*)r->cand, r->raw, (float*)nullptr,
+                         MaskArgs{nullptr, nullptr, nullptr, nullptr}, lnw);
+      hipLaunchKernelGGL(k_rt_normals, dim3(grid), dim3(TILE), 0, s, C, (const RenderObj*)r->objs,
+                         (const Tile*)r->tiles, (const int*)r->ntiles, (const float4*)r->cand, (const float*)r->raw,
+                         r->normals);
+    }
+  }
+  DSR_CHECK(ctx, hipEventRecord(r->ev[1], s));
+  DSR_CHECK(ctx, hipGetLastError());
+  DSR_CHECK(ctx, hipStreamSynchronize(s));
+  // (blocking copies after the synchronise: an error return never leaves a copy in flight to
+  // the caller's buffers or to this frame)
+  DSR_CHECK(ctx, hipMemcpy(depth, r->depth, sizeof(float) * npix, hipMemcpyDeviceToHost));
+  DSR_CHECK(ctx, hipMemcpy(instance, r->inst, sizeof(int) * npix, hipMemcpyDeviceToHost));
+  if (want_n) DSR_CHECK(ctx, hipMemcpy(normals, r->normals, sizeof(float) * 3 * npix, hipMemcpyDeviceToHost));
+  std::vector<int> hcnt((size_t)RC_INTS * std::max(n_obj, 1), 0);
+  RenderStepStats hss{};
+  if (n_obj > 0)
+    DSR_CHECK(ctx, hipMemcpy(hcnt.data(), r->counters, sizeof(int) * RC_INTS * n_obj, hipMemcpyDeviceToHost));
+  DSR_CHECK(ctx, hipMemcpy(&hss, r->ss, sizeof(hss), hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, r->ev[0], r->ev[1]) == hipSuccess) st.resolve_ms = ms;
+  st.steps_run = hss.steps_run;
+  st.decoded = hss.decoded;
+  st.max_live_last = hss.max_live_last;
+  r->st = st;
+  if (per_obj)
+    for (int i = 0; i < n_obj; ++i) {
+      dsr_render_object_out& o = per_obj[i];
+      o.status = status[i];
+      std::memcpy(o.rect, &rects[(size_t)4 * i], sizeof(o.rect));
+      o.n_rays = ho[i].w * ho[i].h;
+      o.n_ball = hcnt[(size_t)i * RC_INTS + RC_BALL];
+      o.n_hit = hcnt[(size_t)i * RC_INTS + RC_HIT];
+      o.n_unconverged = hcnt[(size_t)i * RC_INTS + RC_UNCONV];
+      o.n_visible = hcnt[(size_t)i * RC_INTS + RC_VISIBLE];
+    }
   return 0;
 }
 

@@ -143,6 +143,47 @@ static void no_device_paths(void) {
     CHECK(dsr_reconstruct_views(NULL, NULL, NULL, 1, &vin, &vout, NULL, &fv, NULL) < 0, "views: moved view 0 accepted");
     CHECK(fv == 7, "views: fail_view written by a rejected call");
   }
+  {
+    /* the renderer: null arguments, and the host-only rectangle rule (dsr_render_layout) — a
+       centred object, one off-screen, one in front of the near plane, then a bad camera, a bad
+       last row and a reflected pose */
+    dsr_camera cam = {48, 36, 120.f, 120.f, 23.5f, 17.5f};
+    dsr_renderer* rr = (dsr_renderer*)&cam;           /* must come back NULL-free: never written */
+    CHECK(dsr_renderer_create(NULL, NULL, &cam, &rr) < 0, "renderer_create(NULL ctx) accepted");
+    CHECK(dsr_renderer_create(NULL, NULL, NULL, NULL) < 0, "renderer_create(NULL) accepted");
+    CHECK(dsr_renderer_destroy(NULL) == 0, "renderer_destroy(NULL)");
+    CHECK(dsr_renderer_stats_get(NULL, NULL) < 0, "renderer_stats_get(NULL) accepted");
+    CHECK(dsr_renderer_render(NULL, NULL, 0, NULL, NULL, NULL, NULL, NULL) < 0, "renderer_render(NULL) accepted");
+    dsr_render_object ro[3];
+    memset(ro, 0, sizeof(ro));
+    for (int k = 0; k < 3; ++k)
+      for (int i = 0; i < 4; ++i) ro[k].t_cam_obj[i * 5] = 1.f;
+    ro[0].t_cam_obj[11] = 15.f;
+    ro[1].t_cam_obj[3] = 30.f; ro[1].t_cam_obj[11] = 15.f;
+    ro[2].t_cam_obj[11] = 1.005f;
+    int rect[12], status[3];
+    CHECK(dsr_render_layout(&cam, 0.01f, 3, ro, rect, status) == 0, "render_layout failed");
+    CHECK(status[0] == DSR_RENDER_OK && status[1] == DSR_RENDER_OFFSCREEN && status[2] == DSR_RENDER_SKIP_NEAR,
+          "render_layout statuses %d %d %d", status[0], status[1], status[2]);
+    /* (0 -+ 1) / (15 -+ 1) * 120 = -+8.57 about 23.5 / 17.5 */
+    CHECK(rect[0] == 14 && rect[1] == 8 && rect[2] == 33 && rect[3] == 27, "render_layout rect %d %d %d %d", rect[0],
+          rect[1], rect[2], rect[3]);
+    CHECK(rect[4] == 0 && rect[6] == -1 && rect[8] == 0 && rect[11] == -1, "render_layout empty rects");
+    CHECK(dsr_render_layout(&cam, 0.01f, 0, NULL, NULL, NULL) == 0, "render_layout(n_obj 0)");
+    CHECK(dsr_render_layout(NULL, 0.01f, 0, NULL, NULL, NULL) < 0, "render_layout(NULL camera) accepted");
+    CHECK(dsr_render_layout(&cam, 0.01f, 1, ro, NULL, status) < 0, "render_layout(NULL rect) accepted");
+    cam.fx = 0.f;
+    CHECK(dsr_render_layout(&cam, 0.01f, 1, ro, rect, status) < 0, "render_layout(fx 0) accepted");
+    cam.fx = 120.f;
+    cam.height = 0;
+    CHECK(dsr_render_layout(&cam, 0.01f, 1, ro, rect, status) < 0, "render_layout(height 0) accepted");
+    cam.height = 36;
+    ro[0].t_cam_obj[15] = 2.f;
+    CHECK(dsr_render_layout(&cam, 0.01f, 1, ro, rect, status) < 0, "render_layout(last row) accepted");
+    ro[0].t_cam_obj[15] = 1.f;
+    ro[0].t_cam_obj[0] = -1.f;
+    CHECK(dsr_render_layout(&cam, 0.01f, 1, ro, rect, status) < 0, "render_layout(reflection) accepted");
+  }
   dsr_ctx* c = NULL;
   const int rc2 = dsr_ctx_create(-7, &c);
   CHECK(rc2 < 0 && c == NULL, "ctx_create(-7) = %d", rc2);
@@ -199,6 +240,71 @@ static void live_error_paths(dsr_ctx* ctx, const dsr_decoder* dec, const float* 
   CHECK(dsr_sdf_eval(ctx, dec, NULL, NULL, 4, NULL, NULL) < 0, "sdf_eval NULLs accepted");
   dsr_mesher* m = NULL;
   CHECK(dsr_mesher_create(ctx, dec, NULL, 8, &m) < 0 && m == NULL, "mesher without grid accepted");
+  /* the renderer: refused cameras and parameters, then a 32 x 24 image of two objects (the zero
+     code) twice — the same bytes, consistent counts — and an empty call */
+  {
+    dsr_camera cam = {32, 24, 0.f, 80.f, 15.5f, 11.5f};
+    dsr_renderer* r = NULL;
+    CHECK(dsr_renderer_create(ctx, dec, &cam, &r) < 0 && r == NULL, "fx 0 accepted");
+    CHECK(strlen(dsr_last_error(ctx)) > 0, "no message");
+    cam.fx = 80.f;
+    cam.width = -4;
+    CHECK(dsr_renderer_create(ctx, dec, &cam, &r) < 0 && r == NULL, "width -4 accepted");
+    cam.width = 32;
+    CHECK(dsr_renderer_create(ctx, dec, &cam, &r) == 0 && r != NULL, "renderer_create: %s", dsr_last_error(ctx));
+    static const float zero_code[DSR_CODE_LEN] = {0};
+    dsr_render_object ro[2];
+    memset(ro, 0, sizeof(ro));
+    for (int k = 0; k < 2; ++k) {
+      for (int i = 0; i < 3; ++i) ro[k].t_cam_obj[i * 5] = 2.f;      /* scale 2 */
+      ro[k].t_cam_obj[15] = 1.f;
+      ro[k].t_cam_obj[3] = k ? 1.5f : -1.5f;
+      ro[k].t_cam_obj[11] = 10.f + 2.f * k;
+      ro[k].code = zero_code;
+    }
+    dsr_render_params rp;
+    memset(&rp, 0, sizeof(rp));                                    /* zeros = defaults */
+    float depth[2][32 * 24], nrm[32 * 24 * 3];
+    int inst[2][32 * 24];
+    dsr_render_object_out po[2];
+    rp.max_steps = 257;
+    CHECK(dsr_renderer_render(r, &rp, 2, ro, depth[0], inst[0], NULL, po) < 0, "max_steps 257 accepted");
+    rp.max_steps = 0;
+    rp.hit_eps = -1.f;
+    CHECK(dsr_renderer_render(r, &rp, 2, ro, depth[0], inst[0], NULL, po) < 0, "hit_eps -1 accepted");
+    rp.hit_eps = 0.f;
+    CHECK(dsr_renderer_render(r, &rp, 2, ro, NULL, inst[0], NULL, po) < 0, "NULL depth accepted");
+    rp.normals = 1;
+    CHECK(dsr_renderer_render(r, &rp, 2, ro, depth[0], inst[0], NULL, po) < 0, "normals without a buffer accepted");
+    ro[1].t_cam_obj[15] = 0.f;
+    CHECK(dsr_renderer_render(r, &rp, 2, ro, depth[0], inst[0], nrm, po) < 0, "bad last row accepted");
+    ro[1].t_cam_obj[15] = 1.f;
+    ro[1].code = NULL;
+    CHECK(dsr_renderer_render(r, &rp, 2, ro, depth[0], inst[0], nrm, po) < 0, "NULL code accepted");
+    ro[1].code = zero_code;
+    for (int k = 0; k < 2; ++k)
+      CHECK(dsr_renderer_render(r, &rp, 2, ro, depth[k], inst[k], nrm, po) == 0, "render: %s", dsr_last_error(ctx));
+    CHECK(memcmp(depth[0], depth[1], sizeof(depth[0])) == 0 && memcmp(inst[0], inst[1], sizeof(inst[0])) == 0,
+          "render not reproducible");
+    int vis[2] = {0, 0}, none = 0;
+    for (int i = 0; i < 32 * 24; ++i) {
+      CHECK(inst[0][i] >= -1 && inst[0][i] < 2 && (inst[0][i] < 0) == (depth[0][i] == 0.f), "pixel %d", i);
+      if (inst[0][i] >= 0) ++vis[inst[0][i]]; else ++none;
+    }
+    for (int k = 0; k < 2; ++k) {
+      CHECK(po[k].status == DSR_RENDER_OK && po[k].n_visible == vis[k] && po[k].n_hit >= vis[k] && vis[k] > 0,
+            "object %d: status %d visible %d / %d hit %d", k, po[k].status, po[k].n_visible, vis[k], po[k].n_hit);
+      CHECK(po[k].n_rays >= po[k].n_ball && po[k].n_ball >= po[k].n_hit + po[k].n_unconverged, "object %d counts", k);
+    }
+    dsr_render_stats rs;
+    CHECK(dsr_renderer_stats_get(r, &rs) == 0 && rs.n_obj == 2 && rs.n_passes == 1 && rs.steps_run >= 1 &&
+              rs.steps_run <= 48 && rs.decoded >= po[0].n_ball + po[1].n_ball,
+          "render stats");
+    CHECK(dsr_renderer_render(r, &rp, 0, NULL, depth[1], inst[1], nrm, NULL) == 0, "empty render: %s", dsr_last_error(ctx));
+    for (int i = 0; i < 32 * 24; ++i) CHECK(depth[1][i] == 0.f && inst[1][i] == -1, "empty render pixel %d", i);
+    CHECK(none > 0, "no empty pixel");
+    CHECK(dsr_renderer_destroy(r) == 0, "renderer_destroy");
+  }
 }
 
 int main(int argc, char** argv) {

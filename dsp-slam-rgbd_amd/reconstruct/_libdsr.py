@@ -121,6 +121,37 @@ class MesherStats(C.Structure):
                 ("exact_ms", C.c_double), ("mc_ms", C.c_double)]
 
 
+class Camera(C.Structure):
+    """dsr_camera: a zero-skew pinhole; pixel (u, v) has the ray ((u-cx)/fx, (v-cy)/fy, 1)."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float)]
+
+
+class RenderParams(C.Structure):
+    """dsr_render_params: zeros = defaults (hit_eps 1e-4, max_steps 48, damp 1, near 0.01)."""
+    _fields_ = [("hit_eps", C.c_float), ("max_steps", C.c_int), ("damp", C.c_float), ("near", C.c_float),
+                ("normals", C.c_int)]
+
+
+class RenderObject(C.Structure):
+    _fields_ = [("t_cam_obj", C.c_float * 16), ("code", FP)]
+
+
+class RenderObjectOut(C.Structure):
+    _fields_ = [("status", C.c_int), ("rect", C.c_int * 4), ("n_rays", C.c_int), ("n_ball", C.c_int),
+                ("n_hit", C.c_int), ("n_unconverged", C.c_int), ("n_visible", C.c_int)]
+
+
+class RenderStats(C.Structure):
+    """dsr_render_stats: the last dsr_renderer_render call of a renderer (include/dsr.h)."""
+    _fields_ = [("n_obj", C.c_int), ("n_passes", C.c_int), ("steps_run", C.c_int), ("decoded", C.c_longlong),
+                ("max_live_last", C.c_int), ("setup_ms", C.c_double), ("march_ms", C.c_double),
+                ("resolve_ms", C.c_double)]
+
+
+RENDER_OK, RENDER_OFFSCREEN, RENDER_SKIP_NEAR = 0, 1, 2   # include/dsr.h DSR_RENDER_*
+
+
 #: dsr_batch_lite_diag record layout (csrc/dsr_dev.hpp: STD_*)
 LITE_DIAG_FIELDS = ("broken_blocks", "recorded", "block", "wave", "counter", "target", "observed", "tile_iter",
                     "hw_id", "xcc_id", "polls", "real_ticks")
@@ -178,11 +209,18 @@ SIGNATURES = {
     "dsr_mesher_stats_get": (C.c_int, [C.c_void_p, C.POINTER(MesherStats)]),
     "dsr_mesher_peek": (C.c_int, [C.c_void_p, C.c_int, FP, FP, C.POINTER(C.c_ubyte)]),
     "dsr_mc_volume": (C.c_int, [C.c_void_p, FP, C.c_int, C.c_float, FP, C.c_int, IP, C.c_int, IP, IP]),
+    "dsr_renderer_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.POINTER(C.c_void_p)]),
+    "dsr_renderer_render": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.POINTER(RenderObject),
+                                      FP, IP, FP, C.POINTER(RenderObjectOut)]),
+    "dsr_renderer_stats_get": (C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
+    "dsr_renderer_destroy": (C.c_int, [C.c_void_p]),
+    "dsr_render_layout": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_int, C.POINTER(RenderObject), IP, IP]),
 }
 
 #: entry points added without an ABI number change: callers detect them by the symbol, so a
 #: library of the same ABI number built before them still loads (A/B runs under DSR_LIB)
-BY_SYMBOL = ("dsr_reconstruct_views",)
+BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_render", "dsr_renderer_stats_get",
+             "dsr_renderer_destroy", "dsr_render_layout")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

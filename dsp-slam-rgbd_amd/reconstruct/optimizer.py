@@ -669,3 +669,79 @@ class MeshExtractor(object):
         ctx.check(ctx.lib.dsr_mesher_peek(self._h, int(slot), L.fptr(lite), L.fptr(final),
                                           flags.ctypes.data_as(C.POINTER(C.c_ubyte))), "dsr_mesher_peek")
         return lite, final, flags
+
+
+class SdfRenderer(object):
+    """Depth, instance and normal images of reconstructed objects, sphere-traced over the decoder
+    on device (dsr_renderer_*).  Replaces the reference's mesh + OpenGL path
+    (ObjectRenderer::SetupCamera / Render, src/ObjectRenderer.cc:82-125) without a mesh: the
+    camera is a zero-skew pinhole, pixel (u, v) has the ray ((u-cx)/fx, (v-cy)/fy, 1), depth is
+    z-depth (``get_rays``, loss_utils.py:23-37)."""
+
+    def __init__(self, decoder, width, height, fx, fy, cx, cy, code_len=64):
+        self.decoder = decoder
+        self.code_len = code_len
+        self.width, self.height = int(width), int(height)
+        ctx = decoder.ctx
+        if not hasattr(ctx.lib, "dsr_renderer_create"):
+            raise L.DsrError("this libdsr was built without dsr_renderer_* (no fallback)")
+        cam = L.Camera(self.width, self.height, float(fx), float(fy), float(cx), float(cy))
+        h = C.c_void_p()
+        ctx.check(ctx.lib.dsr_renderer_create(ctx.handle, decoder.handle, C.byref(cam), C.byref(h)),
+                  "dsr_renderer_create")
+        self._h = h
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self.decoder.ctx.lib.dsr_renderer_destroy(h)
+            except Exception:
+                pass
+        self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def render(self, objects, normals=False, **params):
+        """``objects``: a list of ``(t_cam_obj (4,4), code)``.  ``params``: hit_eps, max_steps, damp,
+        near (unset or 0 = the defaults 1e-4, 48, 1, 0.01).  Returns depth (H,W) f32 (0 = nothing
+        hit), instance (H,W) i32 (index into ``objects``, -1 = nothing hit), normals (H,W,3) f32 in
+        the camera frame or None, and ``objects``: per object its status (0 rendered, 1 off-screen,
+        2 skipped at the near plane), rect (u_min, v_min, u_max, v_max), n_rays, n_ball, n_hit,
+        n_unconverged and n_visible."""
+        if self._h is None:
+            raise L.DsrError("renderer is closed")
+        unknown = set(params) - {"hit_eps", "max_steps", "damp", "near"}
+        if unknown:
+            raise TypeError(f"unknown render parameters: {sorted(unknown)}")
+        ctx = self.decoder.ctx
+        n = len(objects)
+        p = L.RenderParams(float(params.get("hit_eps", 0.0)), int(params.get("max_steps", 0)),
+                           float(params.get("damp", 0.0)), float(params.get("near", 0.0)), int(bool(normals)))
+        ins = (L.RenderObject * max(n, 1))()
+        keep = []
+        for i, (t, code) in enumerate(objects):
+            t = np.ascontiguousarray(np.asarray(t, np.float32).reshape(16))
+            c = _code(code, self.code_len)
+            keep.append(c)
+            ins[i].t_cam_obj[:] = t.tolist()
+            ins[i].code = L.fptr(c)
+        outs = (L.RenderObjectOut * max(n, 1))()
+        depth = np.zeros((self.height, self.width), np.float32)
+        inst = np.zeros((self.height, self.width), np.int32)
+        nrm = np.zeros((self.height, self.width, 3), np.float32) if normals else None
+        ctx.check(ctx.lib.dsr_renderer_render(self._h, C.byref(p), n, ins, L.fptr(depth), L.iptr(inst),
+                                              L.fptr(nrm), outs), "dsr_renderer_render")
+        recs = [ForceKeyErrorDict(status=o.status, rect=tuple(o.rect), n_rays=o.n_rays, n_ball=o.n_ball,
+                                  n_hit=o.n_hit, n_unconverged=o.n_unconverged, n_visible=o.n_visible)
+                for o in outs[:n]]
+        return ForceKeyErrorDict(depth=depth, instance=inst, normals=nrm, objects=recs)
+
+    def stats(self):
+        """dsr_render_stats of the last ``render`` call, as a dict."""
+        st = L.RenderStats()
+        rc = self.decoder.ctx.lib.dsr_renderer_stats_get(self._h, C.byref(st))
+        if rc != 0:
+            raise L.DsrError(f"dsr_renderer_stats_get failed ({rc})")
+        return {k: getattr(st, k) for k, _ in L.RenderStats._fields_}

@@ -405,6 +405,74 @@ int dsr_mesher_peek(dsr_mesher* m, int slot, float* lite_vol, float* final_vol, 
 int dsr_mc_volume(dsr_ctx* ctx, const float* vol, int vol_dim, float level, float* verts, int vcap,
                   int* faces, int fcap, int* n_verts, int* n_faces);
 
+/* ---- sphere-traced depth / instance / normal images of reconstructed objects: replaces
+ * ObjectRenderer::SetupCamera / Render (src/ObjectRenderer.cc:82-125, the reference's mesh +
+ * OpenGL rasteriser, include/Renderer.hpp) with a tracer over the decoder itself — no mesh, no
+ * grid (DESIGN.md 3.6b states the algorithm exactly).  Callers detect these entry points by
+ * symbol; the ABI number is unchanged.
+ * Camera: pinhole, zero skew; pixel (u, v) (integers) has the ray ((u-cx)/fx, (v-cy)/fy, 1), so
+ * the depth image holds z-depth, the convention of dsr_object_in.depth. */
+typedef struct { int width, height; float fx, fy, cx, cy; } dsr_camera;
+/* zeros = defaults: hit_eps 1e-4, max_steps 48, damp 1, near 0.01; normals != 0 renders normals */
+typedef struct { float hit_eps; int max_steps; float damp; float near; int normals; } dsr_render_params;
+typedef struct {
+  float t_cam_obj[16];            /* object->camera Sim(3), row-major */
+  const float* code;              /* (code_len,) */
+} dsr_render_object;
+enum {
+  DSR_RENDER_OK = 0,
+  DSR_RENDER_OFFSCREEN = 1,       /* the ball's rectangle misses the image: a valid object, zero rays */
+  DSR_RENDER_SKIP_NEAR = 2        /* the ball reaches in front of the near plane: skipped, zero rays */
+};
+typedef struct {
+  int status;                     /* DSR_RENDER_* */
+  int rect[4];                    /* u_min, v_min, u_max, v_max (inclusive); 0, 0, -1, -1 without rays */
+  int n_rays;                     /* pixels of the rectangle */
+  int n_ball;                     /* rays that enter the unit ball */
+  int n_hit;                      /* rays that found the surface */
+  int n_unconverged;              /* rays still marching after max_steps (counted as misses) */
+  int n_visible;                  /* the object's pixels in the final instance image */
+} dsr_render_object_out;
+typedef struct {
+  int n_obj, n_passes;
+  int steps_run;                  /* 1 + the last march step that had a live ray */
+  long long decoded;              /* decoder evaluations of the march: sum over steps of the live rays */
+  int max_live_last;              /* live rays that entered that last step */
+  double setup_ms, march_ms, resolve_ms;   /* device events, summed over the passes; resolve
+                                              includes the normal pass */
+} dsr_render_stats;
+
+typedef struct dsr_renderer dsr_renderer;
+/* Replaces ObjectRenderer::SetupCamera (src/ObjectRenderer.cc:82-125): binds a camera and the ray
+ * buffers for 2 x width x height rays to a decoder.  Errors: null arguments, non-positive image
+ * size or focal length (checked before the device is touched). */
+int dsr_renderer_create(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_camera* cam, dsr_renderer** out);
+/* Replaces ObjectRenderer::Render (src/ObjectRenderer.cc:82-125) for n_obj objects at once:
+ * depth (height x width float32, 0 where nothing was hit), instance (height x width int32, the
+ * index of the nearest hit object, -1 where none; ties go to the lower index), normals (NULL or
+ * height x width x 3, camera frame, unit, 0 where nothing was hit; filled only when
+ * params->normals != 0), per_obj (NULL or n_obj records).  Objects are taken in input order into
+ * passes whose rectangles fit the ray buffers; the whole march of a pass is enqueued without a
+ * host round trip and synchronised once.  Every sample is decoded exactly (k_mlp_fwd16), and the
+ * images are bitwise reproducible and independent of which other objects share the call.
+ * Errors: null arguments, max_steps outside 1..256, hit_eps < 0 (0 = default), a t_cam_obj whose
+ * last row is not 0 0 0 1 or whose determinant is <= 0.  n_obj == 0 returns an empty image. */
+int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_obj,
+                        const dsr_render_object* objs, float* depth, int* instance, float* normals,
+                        dsr_render_object_out* per_obj);
+/* the last dsr_renderer_render call (no counterpart in ObjectRenderer::Render, src/ObjectRenderer.cc:82-125) */
+int dsr_renderer_stats_get(const dsr_renderer* r, dsr_render_stats* st);
+int dsr_renderer_destroy(dsr_renderer* r);
+/* Host only, no device: the rectangles (n_obj x 4, as dsr_render_object_out.rect) and statuses
+ * (n_obj) dsr_renderer_render will use — the image bounds ObjectRenderer::SetupCamera / Render
+ * (src/ObjectRenderer.cc:82-125) leave to OpenGL's clipping.  The ball of object i has centre
+ * c = t_cam_obj[:3,3] and radius rho = det(R)^(1/3); c_z - rho < near skips it; otherwise
+ * u_min = floor(cx + fx min), u_max = ceil(cx + fx max) over (c_x -+ rho) / (c_z -+ rho), the same
+ * for v, clipped to the image.  near <= 0 means the default 0.01.  Returns < 0 for a bad argument
+ * or pose (no message: there is no context). */
+int dsr_render_layout(const dsr_camera* cam, float near, int n_obj, const dsr_render_object* objs,
+                      int* rect, int* status);
+
 /* ---- multi-GPU from one process: replaces the per-detection loop
  * LocalMapping_util.cc:165-206 spread over devices.  ctx[g] / dec[g] are one context and
  * its decoder per device; objects are LPT-partitioned (cost n_rays*M + n_pts), each
