@@ -151,27 +151,30 @@ static JacKernel jac_kernel_for(const DevDecoder& D) {
 // 2/3/4 k steps, +8 static activation scale, +64 ring carried across layers (88), +128
 // staggered wave groups (216: k_mlp_fwd_lite_st, bitwise equal to 88), +256 unscaled lite
 // weights with the bias in the accumulator and a packed fp16 ReLU epilogue (472), +1024
-// swizzled H image (1496, default: 2-way instead of 4-way epilogue store conflicts,
-// bitwise equal to 472).  18 and 984 are timing experiments whose results are invalid, and
-// 216 (staggered groups with the scaled-weight epilogue) expired its bounded event waits
-// on some round-2 builds for a cause never isolated (git history, round 2-3): all three exist only in
-// a -DDSR_LITE_EXPERIMENTS build, never in the shipped library
+// swizzled H image (1496: 2-way instead of 4-way epilogue store conflicts, bitwise equal to
+// 472), +2048 the B-fragment ring pinned 12 MFMAs ahead of its use, two B base registers and
+// no reads past the last k step (3544, default: gemm_lite_r, bitwise equal to 1496).  18 and
+// 984 are timing experiments whose results are invalid, and 216 (staggered groups with the
+// scaled-weight epilogue) expired its bounded event waits on some round-2 builds for a cause
+// never isolated (git history, round 2-3): all three exist only in a -DDSR_LITE_EXPERIMENTS
+// build, never in the shipped library
 using LiteKernel = void (*)(DevDecoder, const Tile*, const int*, const ObjDesc*, const float4*, const float*,
                             const float*, float*, ErtArgs);
 #ifndef DSR_DEFAULT_LITE_VARIANT
-#define DSR_DEFAULT_LITE_VARIANT 1496
+#define DSR_DEFAULT_LITE_VARIANT 3544
 #endif
 static int lite_variant() {
   const char* e = hook_env("DSR_LITE_VARIANT");
   return e ? atoi(e) : DSR_DEFAULT_LITE_VARIANT;
 }
-// the lite variant lite_kernel() dispatches for the environment's setting (unknown numbers run 1496)
+// the lite variant lite_kernel() dispatches for the environment's setting (unknown numbers run
+// 1496, the schedule before the pinned ring)
 static int lite_variant_dispatched() {
   switch (lite_variant()) {
 #ifdef DSR_LITE_EXPERIMENTS
     case 18: case 984: case 216: case 16: case 32: case 40: case 48: case 56: case 24: case 88:
 #endif
-    case 472: return lite_variant();
+    case 472: case 3544: return lite_variant();
   }
   return 1496;
 }
@@ -192,6 +195,7 @@ static LiteKernel lite_kernel() {
     case 88: return k_mlp_fwd_lite<true, 88>;
 #endif
     case 472: return k_mlp_fwd_lite_st<true, 88 + 256>;
+    case 3544: return k_mlp_fwd_lite_st<true, 88 + 256 + 1024 + 2048>;
   }
   return k_mlp_fwd_lite_st<true, 88 + 256 + 1024>;
 }

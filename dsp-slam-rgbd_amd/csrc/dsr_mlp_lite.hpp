@@ -194,12 +194,97 @@ __device__ __forceinline__ void gemm_lite_x(const _Float16* Wl, const _Float16* 
   step(std::integral_constant<int, 1>{}, std::false_type{}, T - 1);
 }
 
+// LV bit11 (lite_ring, on top of the E2 path): gemm_lite_x with the B ring pinned.  Left to
+// itself the compiler folds gemm_lite_x's four B fragments onto two register tuples and sinks
+// each ds_read next to the MFMAs that use it (a read, a wait for it, its four MFMAs, three
+// times per k step), so a wave issuing alone stalls for the LDS latency every block.  Here
+//   * a sched_barrier after each block's read keeps the read of column block cb+3 ahead of the
+//     MFMAs of block cb (12 MFMAs of lead, 4 fragments live, lgkmcnt(3) waits), as gemm16_ring
+//     does for the split kernels;
+//   * the B addresses are two running element offsets (column blocks 0-3 and 4-7: the 1056-byte
+//     pitch puts blocks 4-7 past the 16-bit DS offset of one base), advanced by one k step each;
+//   * the last k step reads no B fragment past the image (gemm_lite_x reads three that nothing
+//     uses) and the next matrix's first A fragments are requested before it like any k step's.
+// Same MFMAs, same operands, same k order per accumulator: values bitwise those of gemm_lite_x.
+template <bool PRIO, int T, int LV, class Hook = NoHook>
+__device__ __forceinline__ void gemm_lite_r(const _Float16* Wl, const _Float16* Wn, int Tn, int w,
+                                            const _Float16* H, floatx4 (&acc)[4][8], half8 (&a)[2][4],
+                                            int lane, Hook hook = Hook{}, const float* bias = nullptr) {
+  static_assert((LV & 256) != 0, "the pinned ring exists for the unscaled (E2) lite weights only");
+  const _Float16* base = Wl + (size_t)(4 * w) * T * 64 * 8;
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), 0, 4 * T * 1024, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<_Float16*>(Wn + (size_t)(4 * w) * Tn * 64 * 8), 0, 4 * Tn * 1024, 0x00020000);
+  const int voff = lane * 16;
+  const int gsw = (LV & 1024) ? ((lane >> 4) ^ (((lane & 15) >> 2) & 1)) : (lane >> 4);
+  int blo = (lane & 15) * PH + 8 * gsw;      // column blocks 0..3 of the current k step
+  int bhi = blo + 64 * PH;                   // column blocks 4..7
+  asm volatile("" : "+v"(blo), "+v"(bhi));   // two registers, not one base and an add per read
+  auto lda = [&](int q, int t) {
+    return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (q * T + t) * 1024, 0));
+  };
+  // block cb of the current k step (NEXT: of the one after it)
+  auto ldb = [&](int cb, bool next) {
+    return *reinterpret_cast<const half8*>(H + (cb < 4 ? blo : bhi) + (cb & 3) * 16 * PH + (next ? 32 : 0));
+  };
+  half8 b[4];
+  // the accumulators start as the bias rows (`bias`: this layer's 512 floats in LDS), one row
+  // block at a time, so 4 bias registers are live at once and none into the first step
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const floatx4 bq = *reinterpret_cast<const floatx4*>(bias + 64 * w + 16 * q + 4 * (lane >> 4));
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) {
+      acc[q][cb] = bq;
+      asm volatile("" : "+v"(acc[q][cb]));   // keep the copy (gemm_lite_x)
+    }
+  }
+#pragma unroll
+  for (int cb = 0; cb < 3; ++cb) b[cb] = ldb(cb, false);
+  auto step = [&](auto J, auto LAST, int t) {
+    constexpr int j = decltype(J)::value;
+    constexpr bool last = decltype(LAST)::value;
+    hook(t);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      a[j ^ 1][q] = last ? __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rn, voff, q * Tn * 1024, 0))
+                         : lda(q, t + 1);
+    if (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) {
+      if (cb + 3 < 8) b[(cb + 3) & 3] = ldb(cb + 3, false);
+      else if (!last) b[(cb + 3) & 3] = ldb(cb - 5, true);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        acc[q][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[j][q], b[cb & 3], acc[q][cb], 0, 0, 0);
+    }
+    if (PRIO) __builtin_amdgcn_s_setprio(0);
+    blo += 32;
+    bhi += 32;
+  };
+  step(std::integral_constant<int, 0>{}, std::false_type{}, 0);
+#pragma unroll 1
+  for (int t0 = 1; t0 < T - 1; t0 += 2) {
+    step(std::integral_constant<int, 1>{}, std::false_type{}, t0);
+    step(std::integral_constant<int, 0>{}, std::false_type{}, t0 + 1);
+  }
+  step(std::integral_constant<int, 1>{}, std::true_type{}, T - 1);
+}
+
 template <bool PRIO, int LV, class Hook = NoHook>
 __device__ __forceinline__ void lite_gemm_x(const _Float16* Wl, int T, const _Float16* Wn, int Tn, int w,
                                             const _Float16* H, floatx4 (&acc)[4][8], half8 (&a)[2][4], int lane,
-                                            Hook hook = Hook{}, const floatx4* ci = nullptr) {
-  if (T != 14) gemm_lite_x<PRIO, 16, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, ci);
-  else gemm_lite_x<PRIO, 14, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, ci);
+                                            Hook hook = Hook{}, const floatx4* ci = nullptr,
+                                            const float* bias = nullptr) {
+  if constexpr ((LV & 2048) != 0) {
+    if (T != 14) gemm_lite_r<PRIO, 16, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, bias);
+    else gemm_lite_r<PRIO, 14, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, bias);
+  } else {
+    if (T != 14) gemm_lite_x<PRIO, 16, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, ci);
+    else gemm_lite_x<PRIO, 14, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, ci);
+  }
 }
 
 // LV (DSR_LITE_VARIANT): bits 4-5 = NB - 1 (ring depth; 0 is read as NB 2), bit3 static
@@ -606,7 +691,7 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
   __syncthreads();                       // the only block-wide barrier
 #ifdef DSR_EXP_STAMP
   unsigned long long stamp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
+  unsigned long long stamp_last = __builtin_amdgcn_s_memtime(), stamp_lk = 0;
 #endif
   int it = 0;
   auto wait = [&](int* c, int target) { st_wait(c, target, sm, it, w); };
@@ -693,16 +778,30 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
 #endif
         if (t == 8) st_signal(&sm.cRlo);
         if (t == lag && grp == 0) st_signal(&sm.cP);
+#ifdef DSR_EXP_STAMP   // the last k step of the GEMM (with the next matrix's first loads), stamp[9]
+        if (t == D.Kf[l] / 32 - 1) {
+          __builtin_amdgcn_sched_barrier(0);
+          stamp_lk = __builtin_amdgcn_s_memtime();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
       };
       const int ln = l < 7 ? l + 1 : 1;  // (after lin7: the next tile's lin1 fragments)
       floatx4 ci[4];                     // E2: this wave's bias rows start the accumulators
-      if constexpr (E2) {
+      if constexpr ((LV & 2048) != 0) {
+        // (the pinned ring seeds the accumulators itself, from sm.bias[l])
+      } else if constexpr (E2) {
         const int g = opaque(threadIdx.x & 63) >> 4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) ci[q] = *reinterpret_cast<const floatx4*>(sm.bias[l] + 64 * w + 16 * q + 4 * g);
       }
       lite_gemm_x<PRIO, LV>(WA[l], D.Kf[l] / 32, WA[ln], D.Kf[ln] / 32, w, sm.H, acc, ring,
-                            opaque(threadIdx.x & 63), hook, ci);
+                            opaque(threadIdx.x & 63), hook, ci, sm.bias[l]);
+#ifdef DSR_EXP_STAMP
+      __builtin_amdgcn_sched_barrier(0);
+      stamp[9] += __builtin_amdgcn_s_memtime() - stamp_lk;
+      __builtin_amdgcn_sched_barrier(0);
+#endif
       st_signal(&sm.cRhi);
       LSTAMP(5)
     };
@@ -869,8 +968,8 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
 #ifdef DSR_EXP_STAMP
   LSTAMP(7)
   if (blockIdx.x < 4 && (threadIdx.x == 0 || threadIdx.x == 256))
-    printf("lite_stamp %d %d %d %llu %llu %llu %llu %llu %llu %llu %llu %llu\n", (int)blockIdx.x, w, it,
-           stamp[0], stamp[1], stamp[2], stamp[3], stamp[4], stamp[5], stamp[6], stamp[7], stamp[8]);
+    printf("lite_stamp %d %d %d %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu\n", (int)blockIdx.x, w, it,
+           stamp[0], stamp[1], stamp[2], stamp[3], stamp[4], stamp[5], stamp[6], stamp[7], stamp[8], stamp[9]);
 #endif
 }
 #undef LSTAMP

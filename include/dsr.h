@@ -180,7 +180,7 @@ typedef struct {
                                      DSR_BATCH_GRAPH capacity batch */
   int fwd_variant;                /* exact-pass kernel (12: split-fp16, the shipped kernel) */
   int jac_variant;                /* Jacobian kernel (12: split-fp16) */
-  int lite_variant;               /* lite-pass kernel (1496 shipped; 0 when the lite pass is off) */
+  int lite_variant;               /* lite-pass kernel (3544 shipped; 0 when the lite pass is off) */
   int split_ring;                 /* A-ring depth of the split kernels (2 shipped).  Only under
                                      DSR_TEST_HOOKS=1 can DSR_FWD_VARIANT / _JAC_VARIANT /
                                      _LITE_VARIANT / _SPLIT_RING move these from the shipped values.

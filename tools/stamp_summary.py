@@ -1,7 +1,8 @@
 """Per-phase cycle shares of the staggered lite kernel from an exp_STAMP.so run.
 
 Usage: python tools/stamp_summary.py gpurun_out/stamp.txt
-(lines `lite_stamp block wave tiles c0..c8` printed by blocks 0-3, waves 0 and 4)
+(lines `lite_stamp block wave tiles c0..c9` printed by blocks 0-3, waves 0 and 4; c9, the last
+k step of every GEMM, is absent from logs of older builds)
 """
 import sys
 
@@ -22,3 +23,5 @@ for w in (0, 4):
         print(f"   {n:32s} {v:.3f}")
     if w == 0:
         print(f"   {'(of GEMM: step-7 wait for B)':32s} {sel[:, 11].sum() / tot:.3f}")
+    if a.shape[1] > 12:
+        print(f"   {'(of GEMM: last k steps)':32s} {sel[:, 12].sum() / tot:.3f}")
