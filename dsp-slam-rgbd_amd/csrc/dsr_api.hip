@@ -147,57 +147,30 @@ static FwdKernel fwd_kernel_for(const DevDecoder& D, int v) {
 static JacKernel jac_kernel_for(const DevDecoder& D) {
   return is_variant(D) ? k_mlp_jac16<true, 2, true> : jac_kernel();
 }
-// Lite-pass variant (DSR_LITE_VARIANT, dsr_mlp_lite.hpp: lite_gemm): 16/32/48 = A ring of
-// 2/3/4 k steps, +8 static activation scale, +64 ring carried across layers (88), +128
-// staggered wave groups (216: k_mlp_fwd_lite_st, bitwise equal to 88), +256 unscaled lite
-// weights with the bias in the accumulator and a packed fp16 ReLU epilogue (472), +1024
-// swizzled H image (1496: 2-way instead of 4-way epilogue store conflicts, bitwise equal to
-// 472), +2048 the B-fragment ring pinned 12 MFMAs ahead of its use, two B base registers and
-// no reads past the last k step (3544, default: gemm_lite_r, bitwise equal to 1496).  18 and
-// 984 are timing experiments whose results are invalid, and 216 (staggered groups with the
-// scaled-weight epilogue) expired its bounded event waits on some round-2 builds for a cause
-// never isolated (git history, round 2-3): all three exist only in a -DDSR_LITE_EXPERIMENTS
-// build, never in the shipped library
+// Lite-pass schedule (DSR_LITE_VARIANT; dsr_mlp_lite.hpp: k_mlp_fwd_lite_st<SWZ, PIN>).  The
+// numbers are names (environment, dsr_stats.lite_variant); all three give bitwise equal values:
+//   472   staggered wave groups, unswizzled H image
+//   1496  472 + swizzled H image (2-way instead of 4-way epilogue store conflicts); what an
+//         unknown number runs
+//   3544  1496 + the B-fragment ring pinned 12 MFMAs ahead of its use (gemm_lite_r); the default
 using LiteKernel = void (*)(DevDecoder, const Tile*, const int*, const ObjDesc*, const float4*, const float*,
                             const float*, float*, ErtArgs);
 #ifndef DSR_DEFAULT_LITE_VARIANT
 #define DSR_DEFAULT_LITE_VARIANT 3544
 #endif
-static int lite_variant() {
+struct LiteSchedule {
+  int number;
+  LiteKernel kernel;
+};
+static const LiteSchedule& lite_schedule() {
+  static const LiteSchedule table[] = {{1496, k_mlp_fwd_lite_st<true, false>},   // first: the fallback
+                                       {472, k_mlp_fwd_lite_st<false, false>},
+                                       {3544, k_mlp_fwd_lite_st<true, true>}};
   const char* e = hook_env("DSR_LITE_VARIANT");
-  return e ? atoi(e) : DSR_DEFAULT_LITE_VARIANT;
-}
-// the lite variant lite_kernel() dispatches for the environment's setting (unknown numbers run
-// 1496, the schedule before the pinned ring)
-static int lite_variant_dispatched() {
-  switch (lite_variant()) {
-#ifdef DSR_LITE_EXPERIMENTS
-    case 18: case 984: case 216: case 16: case 32: case 40: case 48: case 56: case 24: case 88:
-#endif
-    case 472: case 3544: return lite_variant();
-  }
-  return 1496;
-}
-static LiteKernel lite_kernel() {
-  switch (lite_variant()) {
-#ifdef DSR_LITE_EXPERIMENTS
-    // the barrier kernels and the scaled-epilogue staggered kernel read the split weights' hi
-    // pieces, which the shipped packing sign-alternates (SPLIT_ROW_SIGNS, off in this build)
-    case 18: return k_mlp_fwd_lite<true, 18>;
-    case 984: return k_mlp_fwd_lite_st<true, 88 + 256 + 512>;
-    case 216: return k_mlp_fwd_lite_st<true, 88>;
-    case 16: return k_mlp_fwd_lite<true, 16>;
-    case 32: return k_mlp_fwd_lite<true, 32>;
-    case 40: return k_mlp_fwd_lite<true, 40>;
-    case 48: return k_mlp_fwd_lite<true, 48>;
-    case 56: return k_mlp_fwd_lite<true, 56>;
-    case 24: return k_mlp_fwd_lite<true, 24>;
-    case 88: return k_mlp_fwd_lite<true, 88>;
-#endif
-    case 472: return k_mlp_fwd_lite_st<true, 88 + 256>;
-    case 3544: return k_mlp_fwd_lite_st<true, 88 + 256 + 1024 + 2048>;
-  }
-  return k_mlp_fwd_lite_st<true, 88 + 256 + 1024>;
+  const int v = e ? atoi(e) : DSR_DEFAULT_LITE_VARIANT;
+  for (const LiteSchedule& s : table)
+    if (s.number == v) return s;
+  return table[0];
 }
 // DSR_REFINE_ALL=1: the exact pass re-decodes every band sample, also those behind a ray's
 // first certainly-full sample (k_refine_scan)
@@ -1742,7 +1715,8 @@ static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
   const int fv = fwd_variant();
   const FwdKernel fwdk = fwd_kernel_for(D, fv);
   const JacKernel jack = jac_kernel_for(D);
-  const LiteKernel litek = lite_kernel();
+  const LiteSchedule& lites = lite_schedule();
+  const LiteKernel litek = lites.kernel;
   // (the kernels dispatched, as dsr_batch_stats reports them: fwd_kernel / jac_kernel's choice)
   {
     const int fl = fv & 15;
@@ -1750,7 +1724,7 @@ static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
     const int jv = jac_variant();
     b->ran_fwd = is_variant(D) ? 12 : (known ? fv : (fv & ~15));
     b->ran_jac = is_variant(D) ? 12 : ((jv == 8 || jv == 12) ? jv : 0);
-    b->ran_lite = b->lite ? lite_variant_dispatched() : 0;
+    b->ran_lite = b->lite ? lites.number : 0;
     b->ran_ring = is_variant(D) ? 2 : split_ring();
   }
   const int np = (int)b->passes.size() - 1;
@@ -2496,7 +2470,7 @@ static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec) {
   E.audit_log2 = 7;
   E.perturb = 0.0f;
   E.diag = nullptr;
-  hipLaunchKernelGGL(lite_kernel(), dim3(ctx->n_cu), dim3(512), 0, st, D, (const Tile*)dtl, (const int*)dntl,
+  hipLaunchKernelGGL(lite_schedule().kernel, dim3(ctx->n_cu), dim3(512), 0, st, D, (const Tile*)dtl, (const int*)dntl,
                      (const ObjDesc*)ddesc, (const float4*)dc, (const float*)db0, (const float*)db4, dl, E);
   // against the split-fp16 exact pass a lite batch runs (fwd_kernel(12)), whatever a test's
   // DSR_FWD_VARIANT selects: the XCD soft-sync variants (bit 0) need a sync counter this launch
@@ -2894,7 +2868,7 @@ static int mesh_pass(dsr_mesher* m, int ns, float level, bool sign, const ErtArg
     E.refine = b->refine;
     E.audit = 0;
     E.diag = b->diag;
-    hipLaunchKernelGGL(lite_kernel(), dim3(std::min(ctx->n_cu, ns * b->ntl)), dim3(512), 0, s, D,
+    hipLaunchKernelGGL(lite_schedule().kernel, dim3(std::min(ctx->n_cu, ns * b->ntl)), dim3(512), 0, s, D,
                        (const Tile*)b->ltiles, (const int*)b->cnt, (const ObjDesc*)b->desc, (const float4*)b->pts,
                        (const float*)b->b0, (const float*)b->b4, b->lite, E);
     DSR_CHECK(ctx, hipEventRecord(b->ev[1], s));

@@ -42,9 +42,8 @@ constexpr int PH = 528;                      // LDS pitch of the fp16 images (ha
 // accumulators hold -(W h), their rounding leans the other way, and the epilogues multiply them
 // back by row_sign(q) (exact) — half the rows lean up, half down, and no scale survives.  Zero
 // cost: the sign rides on the epilogue's existing unscale multiply.  The lite pass reads its own
-// unsigned fp16 copy (Wl_raw); the DSR_LITE_EXPERIMENTS build (whose old lite variants read the
-// hi pieces) and DSR_EXP_NOSIGN (A/B) pack without signs.
-#if defined(DSR_LITE_EXPERIMENTS) || defined(DSR_EXP_NOSIGN)
+// unsigned fp16 copy (Wl_raw); a DSR_EXP_NOSIGN build (A/B) packs without signs.
+#ifdef DSR_EXP_NOSIGN
 constexpr bool SPLIT_ROW_SIGNS = false;
 #else
 constexpr bool SPLIT_ROW_SIGNS = true;
@@ -267,7 +266,7 @@ __device__ __forceinline__ void gemm16_tile(const half8* __restrict__ A, int T, 
   }
 }
 
-// Ring schedule of the split GEMM (cf. gemm_lite in dsr_mlp_lite.hpp): NB k steps of (hi, lo)
+// Ring schedule of the split GEMM (cf. gemm_lite_x in dsr_mlp_lite.hpp): NB k steps of (hi, lo)
 // A fragments in flight through buffer loads (one wave-uniform descriptor, lane offset in one
 // VGPR, (q, k step, piece) offset in an SGPR), the (hi, lo) B pair of the next column block
 // read from LDS as the current block's MFMAs issue, and the three products of an accumulator

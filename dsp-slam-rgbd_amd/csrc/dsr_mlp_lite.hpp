@@ -4,29 +4,40 @@
 // (loss_utils.py:40-48) and whether |sdf| < th (loss.py:101): for sdf >= th the sample is
 // exactly empty (o = 0), for sdf <= -th exactly full (o = 1), and only the samples in
 // between need their SDF value.  The lite pass decodes every sample with one fp16 MFMA
-// product (hi(W) . hi(H), fp32 accumulate: 1/3 of the split-fp16 MFMA work, half its
-// weight bytes) on 128-point tiles (the hi image alone fits LDS twice as wide, halving
-// the weight stream per point again), and
+// product (fp16(W) . fp16(H), fp32 accumulate: 1/3 of the split-fp16 MFMA work, half its
+// weight bytes) on 128-point tiles (one fp16 image fits LDS twice as wide as the split
+// kernels' two, halving the weight stream per point again), and
 //   * writes its value to `dense` (a value outside the band has the class of the exact one),
 //   * flags the ray dead when sdf <= -th - margin (certainly full: early termination),
 //   * flags the sample for the exact split-fp16 pass when |sdf| < th + margin.
-// The margin bounds the lite pass's error and calibrates itself per object: 0.02 in the
-// first GN iteration, then max(0.005, 8 x the largest |lite - exact| the object's own
-// re-decoded samples have shown so far) — the exact pass measures that error on every
-// band sample it overwrites (max 8.5e-4 over 1.8M samples of 18 shapes offline,
-// tools/cheap_error.py); a margin above 0.1 sends every sample to the exact pass.  The
-// refined samples carry the exact values, so every occupancy, mask and de_do downstream
-// is the split-fp16 one.
+// The margin bounds the lite pass's error and calibrates itself per object (k_solve): th in
+// the first GN iteration, then max(floor, safety x the largest |lite - exact| the object's
+// own re-decoded samples have shown so far; 0.002 and 4) — the exact pass measures that
+// error on every band sample it overwrites; a margin above 0.1 sends every sample to the
+// exact pass.  The refined samples carry the exact values, so every occupancy, mask and
+// de_do downstream is the split-fp16 one.
+//
+// One kernel, k_mlp_fwd_lite_st<SWZ, PIN>, in three schedules that give bitwise equal values
+// (DSR_LITE_VARIANT, dsr_api.hip: lite_schedule):
+//   472   <false, false>  gemm_lite_x, H image unswizzled
+//   1496  <true,  false>  gemm_lite_x, H image swizzled (lite_swz_g)
+//   3544  <true,  true>   gemm_lite_r (B ring pinned), H image swizzled; the default
 // Layout: tile = 128 points, 512 threads; wave w owns rows 64w..64w+63 as 4 x 8 blocks of
-// 16x16 accumulators; LDS image H[128][528] fp16; weights: the hi pieces of the split
-// fragments (one 1 KiB wave-load per row block and k step), streamed from L2 through a ring
-// of NB k steps in flight (gemm_lite).
+// 16x16 accumulators; LDS image H[128][528] fp16; weights: the unscaled fp16 copy D.Wl_raw
+// (one 1 KiB wave-load per row block and k step), streamed from L2 through a ring of two k
+// steps that is carried across layers and tiles; biases and lin8's row in LDS, the bias
+// seeding the accumulators, so an epilogue is a range check, an fp16 convert and a packed
+// ReLU, and no vector global load waits behind the next layer's in-flight weight fragments
+// (vmcnt counts in order).  Activations are stored unscaled: fp16 keeps 11 significant bits
+// over 6e-5..65504, so only the range needs a guard — a tile in which a value reaches 2^15
+// sends all its samples to the exact pass.  (The one-barrier-per-layer kernel these schedules
+// were derived from, and its scaled-weight variants, are in git history; DESIGN.md appendix A.)
 //
 // Register discipline.  The accumulators take 128 of the wave's 256 VGPRs, so every other
-// value live across a GEMM costs ring depth.  Lane-derived values (LDS addresses, shuffle
-// indices, bias offsets) are re-derived per layer from an opaque copy of the lane id
-// (`opaque`), so the compiler cannot hoist them out of the tile loop and keep ~60 of them
-// live through every GEMM (which it otherwise does).  Conditions that single out rows
+// value live across a GEMM costs registers the rings need.  Lane-derived values (LDS
+// addresses, shuffle indices, bias offsets) are re-derived per layer from an opaque copy of
+// the lane id (`opaque`), so the compiler cannot hoist them out of the tile loop and keep ~60
+// of them live through every GEMM (which it otherwise does).  Conditions that single out rows
 // (lin4's xyz rows) are split into a wave-uniform branch + a per-lane select, never a
 // per-element divergent branch.
 #pragma once
@@ -39,125 +50,53 @@ namespace dsr {
 
 constexpr int LTILE = 128;
 
-struct LiteShared {
-  _Float16 H[LTILE * PH];
-  float xyz[LTILE * 4];
-  float red[NWAVE * LTILE];
-  float wmax[NWAVE];
-  int ovf;
-  // LV bit6 (cross-layer prefetch): the epilogue reads its bias from LDS, so no vector global
-  // load waits behind the next layer's in-flight weight fragments (vmcnt counts in order)
-  float bias[8][HID];          // lin0..lin7 (0 and 4: this tile's object, folded code)
-  float w8[HID];
-};
-
-// acc[4][8] = hi(A rows of this wave) . hi(H) over K = 32*T.
-// Ring schedule: NB A-fragment sets in flight (the loads for k step t+NB-1 issue as step t
-// starts, into the set step t-1 released), buffer loads (one wave-uniform descriptor per
-// layer slice, the lane's 16-byte offset in one VGPR, the (q, k step) offset in an SGPR), and
-// a 4-deep B ring: the B fragment of column block cb+3 (of this step or, past the last block,
-// of the next one) is read from LDS as the MFMAs of block cb issue, so 4 B fragments are live.
-// The first step starts the accumulators from an inline zero C operand.
-// LV bit1 (timing experiment, invalid results): every step re-reads step 0's A fragments.
-template <bool PRIO, int T, int NB, int LV>
-__device__ __forceinline__ void gemm_lite(const _Float16* Wl, int w, const _Float16* H, floatx4 (&acc)[4][8],
-                                          int lane) {
-  const _Float16* base = Wl + (size_t)(4 * w) * T * 2 * 64 * 8;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), 0, 4 * T * 2 * 1024, 0x00020000);
-  const int voff = lane * 16;
-  const _Float16* B = H + (lane & 15) * PH + 8 * (lane >> 4);
-  auto lda = [&](int q, int t) {
-    const int so = ((LV & 2) ? q * T : q * T + t) * 2048;
-    return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, so, 0));
-  };
-  auto ldb = [&](int cb, int k32) { return *reinterpret_cast<const half8*>(B + cb * 16 * PH + k32); };
-  half8 a[NB][4], b[4];
-#pragma unroll
-  for (int j = 0; j < NB - 1; ++j)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a[j][q] = lda(q, j);
-#pragma unroll
-  for (int cb = 0; cb < 3; ++cb) b[cb] = ldb(cb, 0);
-  // step t uses ring slot J = t % NB
-  auto step = [&](auto J, auto FIRST, int t) {
-    constexpr int j = decltype(J)::value;
-    if (t + NB - 1 < T) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[(j + NB - 1) % NB][q] = lda(q, t + NB - 1);
-    }
-    const int pc = 32 * t, pn = 32 * (t + 1);   // (k step T: columns 512.. of the 528 pitch, unused)
-    if (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int cb = 0; cb < 8; ++cb) {
-      b[(cb + 3) & 3] = (cb + 3 < 8) ? ldb(cb + 3, pc) : ldb(cb - 5, pn);
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        acc[q][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-            a[j][q], b[cb & 3], decltype(FIRST)::value ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[q][cb], 0, 0, 0);
-    }
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
-  };
-  step(std::integral_constant<int, 0>{}, std::true_type{}, 0);
-  constexpr int TM = 1 + (T - 1) / NB * NB;     // steps 1 .. TM-1 in groups of NB, then the rest
-#pragma unroll 1
-  for (int t0 = 1; t0 < TM; t0 += NB) {
-    [&]<int... J>(std::integer_sequence<int, J...>) {
-      (step(std::integral_constant<int, (1 + J) % NB>{}, std::false_type{}, t0 + J), ...);
-    }(std::make_integer_sequence<int, NB>{});
-  }
-  [&]<int... J>(std::integer_sequence<int, J...>) {
-    (step(std::integral_constant<int, (TM + J) % NB>{}, std::false_type{}, TM + J), ...);
-  }(std::make_integer_sequence<int, T - TM>{});
-}
-
-// gemm_lite with the ring carried across GEMMs (NB = 2; every T is even, so step t of every
-// matrix uses slot t % 2): on entry a[0] holds step 0 of this matrix, and its last step loads
-// step 0 of the NEXT matrix (Wn, Tn k steps) into a[0], so that load's L2 latency hides behind
-// this layer's last MFMAs and the epilogue instead of stalling the next layer's first MFMA.
-// `hook(t)` runs at the start of k step t, before that step's loads (the staggered kernel's
-// event waits and signals, k_mlp_fwd_lite_st); the default does nothing.
+// `hook(t)` of the GEMMs below runs at the start of k step t, before that step's loads (the
+// kernel's event waits and signals); the default does nothing.
 struct NoHook {
   __device__ __forceinline__ void operator()(int) const {}
 };
 
-// LV bit8 (lite_e2): A fragments from the dense unscaled lite copy (D.Wl_raw: 1 KiB per
-// row block and k step instead of the split layout's 2 KiB stride) and the first step's C
-// operand is `ci` (this wave's bias rows) instead of zero, so the epilogue adds no bias.
-template <bool PRIO, int T, int LV, class Hook = NoHook>
+// acc[4][8] = bias rows + fp16(A rows of this wave) . H over K = 32*T, A = Wl (D.Wl_raw[l]:
+// 1 KiB per row block and k step), read with buffer loads (one wave-uniform descriptor per
+// matrix, the lane's 16-byte offset in one VGPR, the (row block, k step) offset in an SGPR).
+// The A ring is two k steps deep and carried across GEMMs (every T is even, so step t of
+// every matrix uses slot t % 2): on entry a[0] holds step 0 of this matrix, and the last step
+// loads step 0 of the NEXT matrix (Wn, Tn k steps) into a[0], so that load's L2 latency hides
+// behind this layer's last MFMAs and the epilogue instead of stalling the next layer's first
+// MFMA.  B ring, 4 deep: the fragment of column block cb+3 (of this step or, past the last
+// block, of the next one) is read from LDS as the MFMAs of block cb issue.
+// `ci`: this wave's bias rows (4 row blocks x the lane's 4 rows).
+// SWZ: H image swizzled — 16-B chunk index bit 0 XOR point bit 2 (lite_swz_g), a per-lane
+// base offset here.
+template <int T, bool SWZ, class Hook = NoHook>
 __device__ __forceinline__ void gemm_lite_x(const _Float16* Wl, const _Float16* Wn, int Tn, int w,
                                             const _Float16* H, floatx4 (&acc)[4][8], half8 (&a)[2][4],
-                                            int lane, Hook hook = Hook{}, const floatx4* ci = nullptr) {
-  constexpr int WS = (LV & 256) ? 1 : 2;     // KiB per (row block, k step)
-  const _Float16* base = Wl + (size_t)(4 * w) * T * WS * 64 * 8;
+                                            int lane, const floatx4* ci, Hook hook = Hook{}) {
+  const _Float16* base = Wl + (size_t)(4 * w) * T * 64 * 8;
   const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), 0, 4 * T * WS * 1024, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), 0, 4 * T * 1024, 0x00020000);
   const int voff = lane * 16;
-  // LV bit10: H image swizzled — 16-B chunk index bit 0 XOR point bit 2 (lite_swz), a
-  // per-lane base offset here
-  const int gsw = (LV & 1024) ? ((lane >> 4) ^ (((lane & 15) >> 2) & 1)) : (lane >> 4);
+  const int gsw = SWZ ? ((lane >> 4) ^ (((lane & 15) >> 2) & 1)) : (lane >> 4);
   const _Float16* B = H + (lane & 15) * PH + 8 * gsw;
   auto lda = [&](int q, int t) {
-    return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (q * T + t) * WS * 1024, 0));
+    return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (q * T + t) * 1024, 0));
   };
   auto ldb = [&](int cb, int k32) { return *reinterpret_cast<const half8*>(B + cb * 16 * PH + k32); };
   half8 b[4];
-  // E2: the accumulators start as the bias rows, copied before the first step — holding the
-  // 16 bias registers live through step 0 instead (its C operand) made the compiler spill
+  // the accumulators start as the bias rows, copied before the first step — holding the 16
+  // bias registers live through step 0 instead (as its C operand) made the compiler spill
   // inside the tile loop: per-tile scratch stores whose dirty lines the weight stream then
   // evicts to HBM (+30 MB written per launch)
-  if constexpr ((LV & 256) != 0) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+  for (int q = 0; q < 4; ++q)
 #pragma unroll
-      for (int cb = 0; cb < 8; ++cb) {
-        acc[q][cb] = ci[q];
-        asm volatile("" : "+v"(acc[q][cb]));   // keep the copy (else folded back into the C operand)
-      }
-  }
+    for (int cb = 0; cb < 8; ++cb) {
+      acc[q][cb] = ci[q];
+      asm volatile("" : "+v"(acc[q][cb]));   // keep the copy (else folded back into the C operand)
+    }
 #pragma unroll
   for (int cb = 0; cb < 3; ++cb) b[cb] = ldb(cb, 0);
-  auto step = [&](auto J, auto FIRST, int t) {
+  auto step = [&](auto J, int t) {
     constexpr int j = decltype(J)::value;
     hook(t);
     if (t + 1 < T) {
@@ -165,59 +104,57 @@ __device__ __forceinline__ void gemm_lite_x(const _Float16* Wl, const _Float16* 
       for (int q = 0; q < 4; ++q) a[j ^ 1][q] = lda(q, t + 1);
     }
     const int pc = 32 * t, pn = 32 * (t + 1);
-    if (PRIO) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) {
       b[(cb + 3) & 3] = (cb + 3 < 8) ? ldb(cb + 3, pc) : ldb(cb - 5, pn);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const floatx4 c0 = floatx4{0.f, 0.f, 0.f, 0.f};
-        acc[q][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-            a[j][q], b[cb & 3], (decltype(FIRST)::value && (LV & 256) == 0) ? c0 : acc[q][cb], 0, 0, 0);
-      }
+      for (int q = 0; q < 4; ++q)
+        acc[q][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[j][q], b[cb & 3], acc[q][cb], 0, 0, 0);
     }
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
   };
-  step(std::integral_constant<int, 0>{}, std::true_type{}, 0);
+  step(std::integral_constant<int, 0>{}, 0);
 #pragma unroll 1
   for (int t0 = 1; t0 < T - 1; t0 += 2) {
-    step(std::integral_constant<int, 1>{}, std::false_type{}, t0);
-    step(std::integral_constant<int, 0>{}, std::false_type{}, t0 + 1);
+    step(std::integral_constant<int, 1>{}, t0);
+    step(std::integral_constant<int, 0>{}, t0 + 1);
   }
   {   // the next matrix's first step, into the slot step T-2 released
     const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(Wn + (size_t)(4 * w) * Tn * WS * 64 * 8), 0, 4 * Tn * WS * 1024, 0x00020000);
+        const_cast<_Float16*>(Wn + (size_t)(4 * w) * Tn * 64 * 8), 0, 4 * Tn * 1024, 0x00020000);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      a[0][q] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rn, voff, q * Tn * WS * 1024, 0));
+      a[0][q] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rn, voff, q * Tn * 1024, 0));
   }
-  step(std::integral_constant<int, 1>{}, std::false_type{}, T - 1);
+  step(std::integral_constant<int, 1>{}, T - 1);
 }
 
-// LV bit11 (lite_ring, on top of the E2 path): gemm_lite_x with the B ring pinned.  Left to
-// itself the compiler folds gemm_lite_x's four B fragments onto two register tuples and sinks
-// each ds_read next to the MFMAs that use it (a read, a wait for it, its four MFMAs, three
-// times per k step), so a wave issuing alone stalls for the LDS latency every block.  Here
+// gemm_lite_x with the B ring pinned.  Left to itself the compiler folds gemm_lite_x's four B
+// fragments onto two register tuples and sinks each ds_read next to the MFMAs that use it (a
+// read, a wait for it, its four MFMAs, three times per k step), so a wave issuing alone stalls
+// for the LDS latency every block.  Here
 //   * a sched_barrier after each block's read keeps the read of column block cb+3 ahead of the
 //     MFMAs of block cb (12 MFMAs of lead, 4 fragments live, lgkmcnt(3) waits), as gemm16_ring
 //     does for the split kernels;
 //   * the B addresses are two running element offsets (column blocks 0-3 and 4-7: the 1056-byte
 //     pitch puts blocks 4-7 past the 16-bit DS offset of one base), advanced by one k step each;
 //   * the last k step reads no B fragment past the image (gemm_lite_x reads three that nothing
-//     uses) and the next matrix's first A fragments are requested before it like any k step's.
+//     uses) and the next matrix's first A fragments are requested before it like any k step's;
+//   * the accumulators are seeded from the bias rows in LDS inside the GEMM (`bias`: this
+//     layer's 512 floats), so the caller holds no bias registers.
 // Same MFMAs, same operands, same k order per accumulator: values bitwise those of gemm_lite_x.
-template <bool PRIO, int T, int LV, class Hook = NoHook>
+template <int T, bool SWZ, class Hook = NoHook>
 __device__ __forceinline__ void gemm_lite_r(const _Float16* Wl, const _Float16* Wn, int Tn, int w,
                                             const _Float16* H, floatx4 (&acc)[4][8], half8 (&a)[2][4],
-                                            int lane, Hook hook = Hook{}, const float* bias = nullptr) {
-  static_assert((LV & 256) != 0, "the pinned ring exists for the unscaled (E2) lite weights only");
+                                            int lane, const float* bias, Hook hook = Hook{}) {
   const _Float16* base = Wl + (size_t)(4 * w) * T * 64 * 8;
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), 0, 4 * T * 1024, 0x00020000);
   const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<_Float16*>(Wn + (size_t)(4 * w) * Tn * 64 * 8), 0, 4 * Tn * 1024, 0x00020000);
   const int voff = lane * 16;
-  const int gsw = (LV & 1024) ? ((lane >> 4) ^ (((lane & 15) >> 2) & 1)) : (lane >> 4);
+  const int gsw = SWZ ? ((lane >> 4) ^ (((lane & 15) >> 2) & 1)) : (lane >> 4);
   int blo = (lane & 15) * PH + 8 * gsw;      // column blocks 0..3 of the current k step
   int bhi = blo + 64 * PH;                   // column blocks 4..7
   asm volatile("" : "+v"(blo), "+v"(bhi));   // two registers, not one base and an add per read
@@ -229,8 +166,8 @@ __device__ __forceinline__ void gemm_lite_r(const _Float16* Wl, const _Float16* 
     return *reinterpret_cast<const half8*>(H + (cb < 4 ? blo : bhi) + (cb & 3) * 16 * PH + (next ? 32 : 0));
   };
   half8 b[4];
-  // the accumulators start as the bias rows (`bias`: this layer's 512 floats in LDS), one row
-  // block at a time, so 4 bias registers are live at once and none into the first step
+  // the accumulators start as the bias rows, one row block at a time, so 4 bias registers are
+  // live at once and none into the first step
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const floatx4 bq = *reinterpret_cast<const floatx4*>(bias + 64 * w + 16 * q + 4 * (lane >> 4));
@@ -250,7 +187,7 @@ __device__ __forceinline__ void gemm_lite_r(const _Float16* Wl, const _Float16* 
     for (int q = 0; q < 4; ++q)
       a[j ^ 1][q] = last ? __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rn, voff, q * Tn * 1024, 0))
                          : lda(q, t + 1);
-    if (PRIO) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) {
       if (cb + 3 < 8) b[(cb + 3) & 3] = ldb(cb + 3, false);
@@ -260,7 +197,7 @@ __device__ __forceinline__ void gemm_lite_r(const _Float16* Wl, const _Float16* 
       for (int q = 0; q < 4; ++q)
         acc[q][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[j][q], b[cb & 3], acc[q][cb], 0, 0, 0);
     }
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     blo += 32;
     bhi += 32;
   };
@@ -273,66 +210,16 @@ __device__ __forceinline__ void gemm_lite_r(const _Float16* Wl, const _Float16* 
   step(std::integral_constant<int, 1>{}, std::true_type{}, T - 1);
 }
 
-template <bool PRIO, int LV, class Hook = NoHook>
-__device__ __forceinline__ void lite_gemm_x(const _Float16* Wl, int T, const _Float16* Wn, int Tn, int w,
-                                            const _Float16* H, floatx4 (&acc)[4][8], half8 (&a)[2][4], int lane,
-                                            Hook hook = Hook{}, const floatx4* ci = nullptr,
-                                            const float* bias = nullptr) {
-  if constexpr ((LV & 2048) != 0) {
-    if (T != 14) gemm_lite_r<PRIO, 16, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, bias);
-    else gemm_lite_r<PRIO, 14, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, bias);
-  } else {
-    if (T != 14) gemm_lite_x<PRIO, 16, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, ci);
-    else gemm_lite_x<PRIO, 14, LV>(Wl, Wn, Tn, w, H, acc, a, lane, hook, ci);
-  }
-}
-
-// LV (DSR_LITE_VARIANT): bits 4-5 = NB - 1 (ring depth; 0 is read as NB 2), bit3 static
-// activation scale (lite_scale), bit6 the NB-2 ring carried across layers and tiles
-// (gemm_lite_x; biases read from LDS), bit1 timing experiment (no A streaming).
-template <bool PRIO, int LV>
-__device__ __forceinline__ void lite_gemm(const _Float16* Wl, int w, int T, const _Float16* H,
-                                          floatx4 (&acc)[4][8], int lane) {
-  constexpr int NB = ((LV >> 4) & 3) == 0 ? 2 : 1 + ((LV >> 4) & 3);
-  if (T != 14) gemm_lite<PRIO, 16, NB, LV>(Wl, w, H, acc, lane);   // K 512
-  else gemm_lite<PRIO, 14, NB, LV>(Wl, w, H, acc, lane);           // K 448 (lin4: h3 | xyz)
-}
-
-// Per-tile activation scale exponent; contains the barrier that ends every wave's reads of H
-// for the GEMM just finished.
-// Default: block max of m (>= 0) -> power of two (act_scale_exp).
-// LV bit3: static scale 2^0 — fp16 keeps 11 significant bits over 6e-5..65504 whatever the
-// tile's max, so the block max only guards the range: no max exchange and no rescale
-// multiply; a tile whose activations reach 2^15 sets `ovf` and all its samples go to the
-// exact pass instead (so the lite pass can never misclassify through an overflow).
-template <int LV>
-__device__ __forceinline__ int lite_scale(float m, float* wmax, int* ovf, int w, int lane) {
-  if constexpr ((LV & 8) != 0) {
-    if (!(m < 32768.f)) *ovf = 1;
-    __syncthreads();
-    return 0;
-  } else {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, xor_lane(m, lane, o));
-    if (lane == 0) wmax[w] = m;
-    __syncthreads();
-    float mm = wmax[0];
-#pragma unroll
-    for (int k = 1; k < NWAVE; ++k) mm = fmaxf(mm, wmax[k]);
-    return act_scale_exp(mm);
-  }
-}
-
-// H swizzle (LV bit10): element (point p, k) at p * PH + (k ^ (8 * ((p >> 2) & 1))).  The
+// H swizzle (SWZ): element (point p, k) at p * PH + (k ^ (8 * ((p >> 2) & 1))).  The
 // 16-lane groups of the epilogue's 8-byte stores (one 4-row slice, 16 points at the 264-dword
 // pitch) hit each bank 4 times unswizzled and twice swizzled; the 16-byte B reads stay
 // conflict-free (their lane groups mix the two slices).  Only a per-lane offset changes.
 __device__ __forceinline__ int lite_swz_g(int g, int c, bool swz) { return swz ? (g ^ (((c >> 2) & 1) << 1)) : g; }
 
-template <bool SWZ = false>
-__device__ __forceinline__ void lite_write(floatx4 (&acc)[4][8], int s, _Float16* H, int w, int lane) {
+// this wave's 64 rows x 128 points of fp32 values, as fp16, into the image
+template <bool SWZ>
+__device__ __forceinline__ void lite_write(floatx4 (&acc)[4][8], _Float16* H, int w, int lane) {
   const int c = lane & 15, g = lite_swz_g(lane >> 4, c, SWZ);
-  const float sc = ldexpf(1.f, s);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int n0 = 64 * w + 16 * q + 4 * g;
@@ -340,205 +227,20 @@ __device__ __forceinline__ void lite_write(floatx4 (&acc)[4][8], int s, _Float16
     for (int cb = 0; cb < 8; ++cb) {
       half4 h;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) h[r] = (_Float16)(accr(acc[q][cb], r) * sc);
+      for (int r = 0; r < 4; ++r) h[r] = (_Float16)accr(acc[q][cb], r);
       *reinterpret_cast<half4*>(H + (16 * cb + c) * PH + n0) = h;
     }
   }
 }
 
-template <bool PRIO, int LV = 16>
-__global__ __launch_bounds__(512) void k_mlp_fwd_lite(DevDecoder D, const Tile* __restrict__ tiles,
-                                                      const int* __restrict__ n_tiles,
-                                                      const ObjDesc* __restrict__ desc,
-                                                      const float4* __restrict__ cand,
-                                                      const float* __restrict__ bias0f,
-                                                      const float* __restrict__ bias4f,
-                                                      float* __restrict__ dense, ErtArgs E) {
-  __shared__ LiteShared sm;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nt = *n_tiles;
-  if ((int)blockIdx.x >= nt) return;     // no tile for this block: skip the prologue (small passes)
-  constexpr bool XL = (LV & 64) != 0;     // ring carried across layers, biases in LDS
-  half8 ring[2][4];
-  if constexpr (XL) {
-    const int tid = opaque(threadIdx.x);
-    for (int e = tid; e < 7 * HID; e += 512) {
-      const int l = e / HID, n = e - l * HID;        // lin1..3, lin5..7, W8
-      if (l < 6) sm.bias[l < 3 ? l + 1 : l + 2][n] = D.bias[l < 3 ? l + 1 : l + 2][n];
-      else sm.w8[n] = D.W8[n];
-    }
-    const int lane = tid & 63;
-    const _Float16* A1 = D.Wh_raw[1] + (size_t)(4 * w) * (D.Kf[1] / 32) * 2 * 64 * 8;
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(A1), 0, 4 * (D.Kf[1] / 32) * 2 * 1024, 0x00020000);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      ring[0][q] = __builtin_bit_cast(
-          half8, __builtin_amdgcn_raw_buffer_load_b128(r1, lane * 16, q * (D.Kf[1] / 32) * 2048, 0));
-  }
-  for (int ti = blockIdx.x; ti < nt; ti += gridDim.x) {
-    const Tile tl = tiles[ti];
-    const ObjDesc d = desc[tl.obj];
-    {
-      const int tid = opaque(threadIdx.x);
-      if (tid < LTILE) {
-        const float4 v = (tid < tl.count) ? cand[d.cand_off + tl.start + tid] : make_float4(0.f, 0.f, 0.f, 0.f);
-        *reinterpret_cast<float4*>(sm.xyz + tid * 4) = v;
-      }
-      if (tid == 0) sm.ovf = 0;
-      if constexpr (XL) {                  // this object's folded lin0 / lin4 biases
-        if (tid < 256) {
-          const float* src = (tid < 128 ? bias0f : bias4f) + tl.obj * HID + 4 * (tid & 127);
-          *reinterpret_cast<float4*>(&sm.bias[tid < 128 ? 0 : 4][4 * (tid & 127)]) =
-              *reinterpret_cast<const float4*>(src);
-        }
-      }
-    }
-    __syncthreads();
-    floatx4 acc[4][8];
-    int sa;
-    // ---- lin0 (3 inputs, fp32 VALU) into the accumulator layout
-    {
-      const int lane = opaque(threadIdx.x & 63), g = lane >> 4, c = lane & 15;
-      const float* bias0 = XL ? sm.bias[0] : bias0f + tl.obj * HID;
-      float m = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n0 = 64 * w + 16 * q + 4 * g;
-        const float4 bb = *reinterpret_cast<const float4*>(bias0 + n0);
-        float wx[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) wx[i] = D.W0x[n0 * 3 + i];
-#pragma unroll
-        for (int cb = 0; cb < 8; ++cb) {
-          const float4 p = *reinterpret_cast<const float4*>(sm.xyz + (16 * cb + c) * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float a = fetch4(bb, r) + ((wx[3 * r] * p.x + wx[3 * r + 1] * p.y) + wx[3 * r + 2] * p.z);
-            const float h = fmaxf(a, 0.f);
-            acc[q][cb][r] = h;
-            m = fmaxf(m, h);
-          }
-        }
-      }
-      sa = lite_scale<LV>(m, sm.wmax, &sm.ovf, w, lane);
-      lite_write(acc, sa, sm.H, w, lane);
-    }
-    __syncthreads();
-    // ---- lin1..lin6
-#pragma unroll 1
-    for (int l = 1; l <= 6; ++l) {
-      const int lane = opaque(threadIdx.x & 63), g = lane >> 4, c = lane & 15;
-      if constexpr (XL)
-        lite_gemm_x<PRIO, LV>(D.Wh_raw[l], D.Kf[l] / 32, D.Wh_raw[l + 1], D.Kf[l + 1] / 32, w, sm.H, acc, ring, lane);
-      else
-        lite_gemm<PRIO, LV>(D.Wh_raw[l], w, D.Kf[l] / 32, sm.H, acc, lane);
-      const float usc = ldexpf(1.f, -(D.sw[l] + sa));
-      const float* bias = XL ? sm.bias[l] : (l == 4) ? bias4f + tl.obj * HID : D.bias[l];
-      float m = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 bb = *reinterpret_cast<const float4*>(bias + 64 * w + 16 * q + 4 * g);
-#pragma unroll
-        for (int cb = 0; cb < 8; ++cb) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x = fmaxf(__builtin_fmaf(accr(acc[q][cb], r), usc, fetch4(bb, r)), 0.f);
-            acc[q][cb][r] = x;
-            m = fmaxf(m, x);
-          }
-        }
-      }
-      if (l == 3 && w == (D.l3 >> 6)) {   // lin4 input = h3 | xyz: rows l3..l3+2 (g 3, r 1..3) <- x, y, z
-        const int xq = (D.l3 >> 4) & 3;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q != xq) continue;
-#pragma unroll
-          for (int cb = 0; cb < 8; ++cb) {
-            const float4 p = *reinterpret_cast<const float4*>(sm.xyz + (16 * cb + c) * 4);
-            const bool on = g == 3;
-            acc[q][cb][1] = on ? p.x : acc[q][cb][1];
-            acc[q][cb][2] = on ? p.y : acc[q][cb][2];
-            acc[q][cb][3] = on ? p.z : acc[q][cb][3];
-            m = fmaxf(m, on ? fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z))) : 0.f);
-          }
-        }
-      }
-      sa = lite_scale<LV>(m, sm.wmax, &sm.ovf, w, lane);
-      lite_write(acc, sa, sm.H, w, lane);
-      __syncthreads();
-    }
-    // ---- lin7 + relu, lin8 dot product, tanh
-    {
-      const int lane = opaque(threadIdx.x & 63), g = lane >> 4, c = lane & 15;
-      if constexpr (XL)     // (the next tile's lin1 fragments: same weights every tile)
-        lite_gemm_x<PRIO, LV>(D.Wh_raw[7], D.Kf[7] / 32, D.Wh_raw[1], D.Kf[1] / 32, w, sm.H, acc, ring, lane);
-      else
-        lite_gemm<PRIO, LV>(D.Wh_raw[7], w, D.Kf[7] / 32, sm.H, acc, lane);
-      const float usc = ldexpf(1.f, -(D.sw[7] + sa));
-      const float* b7 = XL ? sm.bias[7] : D.bias[7];
-      const float* w8p = XL ? sm.w8 : D.W8;
-      float part[8];
-#pragma unroll
-      for (int cb = 0; cb < 8; ++cb) part[cb] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n0 = 64 * w + 16 * q + 4 * g;
-        const float4 bb = *reinterpret_cast<const float4*>(b7 + n0);
-        const float4 w8 = *reinterpret_cast<const float4*>(w8p + n0);
-#pragma unroll
-        for (int cb = 0; cb < 8; ++cb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float v = fmaxf(__builtin_fmaf(accr(acc[q][cb], r), usc, fetch4(bb, r)), 0.f);
-            part[cb] = __builtin_fmaf(fetch4(w8, r), v, part[cb]);
-          }
-      }
-#pragma unroll
-      for (int cb = 0; cb < 8; ++cb) {
-        float s = part[cb];
-        s += xor_lane(s, lane, 16);
-        s += xor_lane(s, lane, 32);
-        if (g == 0) sm.red[w * LTILE + 16 * cb + c] = s;
-      }
-    }
-    __syncthreads();
-    {
-      const int tid = opaque(threadIdx.x);
-      if (tid < tl.count) {
-        float s = sm.red[tid];
-        for (int k = 1; k < NWAVE; ++k) s += sm.red[k * LTILE + tid];
-        float y = tanhf(s + D.b8);
-        const float4 p = *reinterpret_cast<const float4*>(sm.xyz + tid * 4);
-        if (p.x != p.x || p.y != p.y || p.z != p.z || bias0f[tl.obj * HID] != bias0f[tl.obj * HID])
-          y = __builtin_nanf("");
-        const int idx = __float_as_int(p.w);
-        const ObjState& So = E.st[tl.obj];
-        const float margin = So.lite_margin;
-        y = lite_perturb(E, y, idx);
-        dense[d.cand_off + idx] = y;
-        bool full = false;
-        const unsigned char fl = ((LV & 8) && sm.ovf) ? 1 : lite_flag(E, y, idx, margin, So.iters_done, full);
-        if (fl) E.refine[d.cand_off + idx] = fl;                 // band / range guard / audit
-        if (fl != 1 && full) dead_put(E.dead + d.ray_off + idx / E.M, 1);  // certainly full
-#ifdef DSR_EXP_PROV
-        prov_lite(So.iters_done, d.cand_off + idx, d.ray_off + idx / E.M, idx % E.M, y, fl != 1 && full);
-#endif
-      }
-    }
-    __syncthreads();
-  }
-}
-
 // ------------------------------------------------------------------------------------
-// Staggered groups (DSR_LITE_VARIANT bit7, on top of 88's cross-layer ring, static scale and
-// LDS biases).  With one barrier per layer all 8 waves run their epilogues together and the
-// MFMA pipes idle meanwhile.  Here waves 0-3 (group A: rows 0..255 = the next GEMM's k steps
-// 0..7) and waves 4-7 (group B: rows 256..511 = k steps 8..15) synchronise through event
+// Staggered groups.  With one barrier per layer all 8 waves would run their epilogues together
+// and the MFMA pipes idle meanwhile.  Here waves 0-3 (group A: rows 0..255 = the next GEMM's k
+// steps 0..7) and waves 4-7 (group B: rows 256..511 = k steps 8..15) synchronise through event
 // counters in LDS instead, so B can trail A and each SIMD's two waves (w, w+4) overlap one
-// wave's epilogue with the other's MFMAs.  Same MFMAs in the same k order as variant 88, so
-// the lite values are bitwise those of 88.  Events (monotonic; a wave adds 1 per event):
+// wave's epilogue with the other's MFMAs.  The order in which waves run changes no value: every
+// accumulator sees the same MFMAs in the same k order.  Events (monotonic; a wave adds 1 per
+// event):
 //   cH[g]  group g wrote its rows of the current image (or, at lin7, its part of `red`)
 //   cRlo   a wave finished reading k steps 0..7 of a GEMM's input (signalled at step 8)
 //   cRhi   a wave finished the GEMM (all its reads)
@@ -592,9 +294,6 @@ __device__ __forceinline__ void st_expire(int* c, int target, int observed, Lite
 }
 
 __device__ __forceinline__ void st_report(const LiteStShared& sm, int* diag, int w) {
-#ifdef DSR_EXP_NODIAG   // traffic experiment: round 2's wait without the expired-wait record
-  return;
-#endif
   if (diag == nullptr || sm.rec[4] != w || __lane_id() != 0) return;
   atomicAdd(diag + STD_BROKEN, 1);
   if (atomicCAS(diag + STD_CLAIM, 0, 1) != 0) return;
@@ -619,18 +318,11 @@ __device__ __forceinline__ void st_wait(int* c, int target, LiteStShared& sm, in
     if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&sm.broken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))
       break;
     ++n;
-#ifdef DSR_EXP_NODIAG
-    if (n > (1 << DSR_LITE_WAIT_LOG2)) {
-      __hip_atomic_store(&sm.broken, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      break;
-    }
-#else
     if (n == 1024) sm.twait[w] = (unsigned)__builtin_amdgcn_s_memrealtime();   // a long wait: clock it
     if (n > (1 << DSR_LITE_WAIT_LOG2)) {
       st_expire(c, target, v, sm, it, w);
       break;
     }
-#endif
     __builtin_amdgcn_s_sleep(1);
   }
   asm volatile("" ::: "memory");
@@ -648,7 +340,8 @@ __device__ __forceinline__ void st_wait(int* c, int target, LiteStShared& sm, in
 #else
 #define LSTAMP(cat)
 #endif
-template <bool PRIO, int LV>
+// SWZ: the H image is swizzled (lite_swz_g); PIN: the GEMMs run gemm_lite_r, not gemm_lite_x.
+template <bool SWZ, bool PIN>
 __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Tile* __restrict__ tiles,
                                                          const int* __restrict__ n_tiles,
                                                          const ObjDesc* __restrict__ desc,
@@ -662,9 +355,6 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
   const int nt = *n_tiles;
   if ((int)blockIdx.x >= nt) return;     // no tile for this block: skip the prologue (small passes)
   const int lag = E.lag;
-  constexpr bool E2 = (LV & 256) != 0;
-  constexpr int WS = E2 ? 1 : 2;
-  const _Float16* const* WA = E2 ? D.Wl_raw : D.Wh_raw;
   half8 ring[2][4];
   {
     const int tid = opaque(threadIdx.x);
@@ -680,13 +370,13 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
     }
     if (tid == 18) sm.rec[4] = -1;
     const int lane = tid & 63;
-    const _Float16* A1 = WA[1] + (size_t)(4 * w) * (D.Kf[1] / 32) * WS * 64 * 8;
+    const _Float16* A1 = D.Wl_raw[1] + (size_t)(4 * w) * (D.Kf[1] / 32) * 64 * 8;
     const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<_Float16*>(A1), 0, 4 * (D.Kf[1] / 32) * WS * 1024, 0x00020000);
+        const_cast<_Float16*>(A1), 0, 4 * (D.Kf[1] / 32) * 1024, 0x00020000);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       ring[0][q] = __builtin_bit_cast(
-          half8, __builtin_amdgcn_raw_buffer_load_b128(r1, lane * 16, q * (D.Kf[1] / 32) * WS * 1024, 0));
+          half8, __builtin_amdgcn_raw_buffer_load_b128(r1, lane * 16, q * (D.Kf[1] / 32) * 1024, 0));
   }
   __syncthreads();                       // the only block-wide barrier
 #ifdef DSR_EXP_STAMP
@@ -736,10 +426,8 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
           const float4 pt = *reinterpret_cast<const float4*>(xyz + (16 * cb + c) * 4);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float a =
-                E2 ? __builtin_fmaf(wx[3 * r + 2], pt.z,
-                                    __builtin_fmaf(wx[3 * r + 1], pt.y, __builtin_fmaf(wx[3 * r], pt.x, fetch4(bb, r))))
-                   : fetch4(bb, r) + ((wx[3 * r] * pt.x + wx[3 * r + 1] * pt.y) + wx[3 * r + 2] * pt.z);
+            const float a = __builtin_fmaf(
+                wx[3 * r + 2], pt.z, __builtin_fmaf(wx[3 * r + 1], pt.y, __builtin_fmaf(wx[3 * r], pt.x, fetch4(bb, r))));
             const float h = fmaxf(a, 0.f);
             acc[q][cb][r] = h;
             m = fmaxf(m, h);
@@ -750,11 +438,11 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
       LSTAMP(1)
       wait(grp == 0 ? &sm.cRlo : &sm.cRhi, 8 * 7 * it);   // readers of lin7's input
       LSTAMP(2)
-      lite_write<(LV & 1024) != 0>(acc, 0, sm.H, w, lane);
+      lite_write<SWZ>(acc, sm.H, w, lane);
       st_signal(&sm.cH[grp]);
       LSTAMP(3)
     }
-    // ---- lin1..lin7 (lin7: + relu, lin8 dot product -> red)
+    // ---- lin1..lin7 (lin7: + relu, lin8 dot product -> red); gemm(l): acc = b_l + W_l . H
     auto gemm = [&](int l) {
       const int ng = 7 * it + l;         // GEMMs so far, this one included
       const int hs = 4 * (8 * it + l);   // cH count once the input image is complete
@@ -786,17 +474,25 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
         }
 #endif
       };
-      const int ln = l < 7 ? l + 1 : 1;  // (after lin7: the next tile's lin1 fragments)
-      floatx4 ci[4];                     // E2: this wave's bias rows start the accumulators
-      if constexpr ((LV & 2048) != 0) {
-        // (the pinned ring seeds the accumulators itself, from sm.bias[l])
-      } else if constexpr (E2) {
+      // The bias rows start the accumulators: gemm_lite_x takes this wave's in registers (ci),
+      // gemm_lite_r reads them from sm.bias[l] itself.  K = 512, or 448 for lin4 (h3 | xyz).
+      floatx4 ci[4];
+      if constexpr (!PIN) {
         const int g = opaque(threadIdx.x & 63) >> 4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) ci[q] = *reinterpret_cast<const floatx4*>(sm.bias[l] + 64 * w + 16 * q + 4 * g);
       }
-      lite_gemm_x<PRIO, LV>(WA[l], D.Kf[l] / 32, WA[ln], D.Kf[ln] / 32, w, sm.H, acc, ring,
-                            opaque(threadIdx.x & 63), hook, ci, sm.bias[l]);
+      const int ln = l < 7 ? l + 1 : 1;  // (after lin7: the next tile's lin1 fragments)
+      const _Float16 *Wl = D.Wl_raw[l], *Wn = D.Wl_raw[ln];
+      const int T = D.Kf[l] / 32, Tn = D.Kf[ln] / 32;
+      const int lane = opaque(threadIdx.x & 63);
+      if constexpr (PIN) {
+        if (T != 14) gemm_lite_r<16, SWZ>(Wl, Wn, Tn, w, sm.H, acc, ring, lane, sm.bias[l], hook);
+        else gemm_lite_r<14, SWZ>(Wl, Wn, Tn, w, sm.H, acc, ring, lane, sm.bias[l], hook);
+      } else {
+        if (T != 14) gemm_lite_x<16, SWZ>(Wl, Wn, Tn, w, sm.H, acc, ring, lane, ci, hook);
+        else gemm_lite_x<14, SWZ>(Wl, Wn, Tn, w, sm.H, acc, ring, lane, ci, hook);
+      }
 #ifdef DSR_EXP_STAMP
       __builtin_amdgcn_sched_barrier(0);
       stamp[9] += __builtin_amdgcn_s_memtime() - stamp_lk;
@@ -809,76 +505,26 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
     for (int l = 1; l <= 6; ++l) {
       gemm(l);
       const int lane = opaque(threadIdx.x & 63), g = lane >> 4, c = lane & 15;
-      if constexpr (E2) {   // acc = b + W.h already: range max, fp16 convert, packed fp16 ReLU
-        // The range max runs on the bit patterns (signed int order = float order for x >= 0,
-        // every negative below 0, NaN above +inf so it trips the guard): v_max3_i32, no NaN
-        // canonicalisation of the MFMA results that a float max would insert.
-        half4 hv[4][8];
-        int mi = 0;
+      // acc = b + W.h already: range max, fp16 convert, packed fp16 ReLU.
+      // The range max runs on the bit patterns (signed int order = float order for x >= 0,
+      // every negative below 0, NaN above +inf so it trips the guard): v_max3_i32, no NaN
+      // canonicalisation of the MFMA results that a float max would insert.
+      half4 hv[4][8];
+      int mi = 0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int cb = 0; cb < 8; ++cb) {
-            const floatx4 v = acc[q][cb];
-            mi = max(mi, max(__float_as_int(v[0]), __float_as_int(v[1])));
-            mi = max(mi, max(__float_as_int(v[2]), __float_as_int(v[3])));
-            half4 h;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[r] = (_Float16)v[r];
-            hv[q][cb] = __builtin_elementwise_max(h, half4{0, 0, 0, 0});
-          }
-        if (l == 3 && w == (D.l3 >> 6)) {   // lin4 input rows l3..l3+2 <- x, y, z (after the ReLU)
-          const int xq = (D.l3 >> 4) & 3;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            if (q != xq) continue;
-#pragma unroll
-            for (int cb = 0; cb < 8; ++cb) {
-              const float4 pt = *reinterpret_cast<const float4*>(xyz + (16 * cb + c) * 4);
-              const bool on = g == 3;
-              hv[q][cb][1] = on ? (_Float16)pt.x : hv[q][cb][1];
-              hv[q][cb][2] = on ? (_Float16)pt.y : hv[q][cb][2];
-              hv[q][cb][3] = on ? (_Float16)pt.z : hv[q][cb][3];
-              mi = max(mi, on ? __float_as_int(fmaxf(fabsf(pt.x), fmaxf(fabsf(pt.y), fabsf(pt.z)))) : 0);
-            }
-          }
-        }
-        if (!(__int_as_float(mi) < 32768.f)) sm.ovf[p] = it + 1;
-        LSTAMP(6)
-        wait(grp == 0 ? &sm.cRlo : &sm.cRhi, 8 * (7 * it + l));
-        LSTAMP(2)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int cb = 0; cb < 8; ++cb) {
-            if constexpr ((LV & 512) != 0)   // timing experiment (invalid results): conflict-free stores
-              *reinterpret_cast<half4*>(sm.H + (cb * 4 + q) * 2048 + w * 256 + lane * 4) = hv[q][cb];
-            else
-              *reinterpret_cast<half4*>(sm.H + (16 * cb + c) * PH + 64 * w + 16 * q +
-                                        4 * lite_swz_g(g, c, (LV & 1024) != 0)) = hv[q][cb];
-          }
-        st_signal(&sm.cH[grp]);
-        LSTAMP(3)
-        continue;
-      }
-      const float usc = ldexpf(1.f, -D.sw[l]);
-      const float* bias = sm.bias[l];
-      float m = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 bb = *reinterpret_cast<const float4*>(bias + 64 * w + 16 * q + 4 * g);
+      for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int cb = 0; cb < 8; ++cb) {
+          const floatx4 v = acc[q][cb];
+          mi = max(mi, max(__float_as_int(v[0]), __float_as_int(v[1])));
+          mi = max(mi, max(__float_as_int(v[2]), __float_as_int(v[3])));
+          half4 h;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x = fmaxf(__builtin_fmaf(accr(acc[q][cb], r), usc, fetch4(bb, r)), 0.f);
-            acc[q][cb][r] = x;
-            m = fmaxf(m, x);
-          }
+          for (int r = 0; r < 4; ++r) h[r] = (_Float16)v[r];
+          hv[q][cb] = __builtin_elementwise_max(h, half4{0, 0, 0, 0});
         }
-      }
       if (l == 3 && w == (D.l3 >> 6)) {   // lin4 input = h3 | xyz: rows l3..l3+2 (g 3, r 1..3) <- x, y, z
-        const int xq = (D.l3 >> 4) & 3;
+        const int xq = (D.l3 >> 4) & 3;   // (after the ReLU)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           if (q != xq) continue;
@@ -886,36 +532,41 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
           for (int cb = 0; cb < 8; ++cb) {
             const float4 pt = *reinterpret_cast<const float4*>(xyz + (16 * cb + c) * 4);
             const bool on = g == 3;
-            acc[q][cb][1] = on ? pt.x : acc[q][cb][1];
-            acc[q][cb][2] = on ? pt.y : acc[q][cb][2];
-            acc[q][cb][3] = on ? pt.z : acc[q][cb][3];
-            m = fmaxf(m, on ? fmaxf(fabsf(pt.x), fmaxf(fabsf(pt.y), fabsf(pt.z))) : 0.f);
+            hv[q][cb][1] = on ? (_Float16)pt.x : hv[q][cb][1];
+            hv[q][cb][2] = on ? (_Float16)pt.y : hv[q][cb][2];
+            hv[q][cb][3] = on ? (_Float16)pt.z : hv[q][cb][3];
+            mi = max(mi, on ? __float_as_int(fmaxf(fabsf(pt.x), fmaxf(fabsf(pt.y), fabsf(pt.z)))) : 0);
           }
         }
       }
-      if (!(m < 32768.f)) sm.ovf[p] = it + 1;
+      if (!(__int_as_float(mi) < 32768.f)) sm.ovf[p] = it + 1;
+      LSTAMP(6)
       wait(grp == 0 ? &sm.cRlo : &sm.cRhi, 8 * (7 * it + l));
-      lite_write<(LV & 1024) != 0>(acc, 0, sm.H, w, lane);
+      LSTAMP(2)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb)
+          *reinterpret_cast<half4*>(sm.H + (16 * cb + c) * PH + 64 * w + 16 * q + 4 * lite_swz_g(g, c, SWZ)) =
+              hv[q][cb];
       st_signal(&sm.cH[grp]);
+      LSTAMP(3)
     }
     {
       gemm(7);
       const int lane = opaque(threadIdx.x & 63), g = lane >> 4, c = lane & 15;
-      const float usc = ldexpf(1.f, -D.sw[7]);
       float part[8];
 #pragma unroll
       for (int cb = 0; cb < 8; ++cb) part[cb] = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int n0 = 64 * w + 16 * q + 4 * g;
-        const float4 bb = *reinterpret_cast<const float4*>(sm.bias[7] + n0);
         const float4 w8 = *reinterpret_cast<const float4*>(sm.w8 + n0);
 #pragma unroll
         for (int cb = 0; cb < 8; ++cb)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float v = E2 ? __int_as_float(max(__float_as_int(accr(acc[q][cb], r)), 0))  // ReLU on bits
-                               : fmaxf(__builtin_fmaf(accr(acc[q][cb], r), usc, fetch4(bb, r)), 0.f);
+            const float v = __int_as_float(max(__float_as_int(accr(acc[q][cb], r)), 0));   // ReLU on bits
             part[cb] = __builtin_fmaf(fetch4(w8, r), v, part[cb]);
           }
       }
@@ -946,7 +597,6 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
           const ObjState& So = E.st[tl.obj];
           const float margin = So.lite_margin;
           y = lite_perturb(E, y, idx);
-#ifndef DSR_EXP_NOOUT   // traffic experiment (invalid results): no per-sample outputs
           dense[d.cand_off + idx] = y;
           bool full = false;
           const unsigned char fl = (sm.ovf[p] == it + 1 || sm.broken)
@@ -955,9 +605,6 @@ __global__ __launch_bounds__(512) void k_mlp_fwd_lite_st(DevDecoder D, const Til
           if (fl != 1 && full) dead_put(E.dead + d.ray_off + idx / E.M, 1);  // certainly full
 #ifdef DSR_EXP_PROV
           prov_lite(So.iters_done, d.cand_off + idx, d.ray_off + idx / E.M, idx % E.M, y, fl != 1 && full);
-#endif
-#else
-          if (y == 12345.f) dense[d.cand_off + idx] = margin;
 #endif
         }
       }

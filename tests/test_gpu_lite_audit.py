@@ -396,16 +396,18 @@ def test_query_never_waits_for_the_redo(gpu_decoder, monkeypatch):
 
 
 
-def test_stats_report_the_kernels_the_run_dispatched(gpu_decoder, monkeypatch):
+@pytest.mark.parametrize("unknown", ["16", "216"])
+def test_stats_report_the_kernels_the_run_dispatched(gpu_decoder, monkeypatch, unknown):
     """dsr_stats' kernel fields (ABI 10/11) are the kernels the last run
-    dispatched, resolved as it was enqueued — an unknown DSR_LITE_VARIANT runs (and reports) the
-    shipped 1496, and changing the environment between run and stats changes nothing reported."""
+    dispatched, resolved as it was enqueued — an unknown DSR_LITE_VARIANT (16 and 216 once
+    named kernels that are no longer in the library) runs and reports the fallback 1496, and
+    changing the environment between run and stats changes nothing reported."""
     from reconstruct import _libdsr as L
 
     opt = _opt(gpu_decoder, S.KITTI_OPTIM, "KITTI", iters=2)
     objs = [(o.t_cam_obj, o.pts, o.rays, o.depth, None) for o in (S.kitti_object(i) for i in range(2))]
     monkeypatch.setenv("DSR_TEST_HOOKS", "1")
-    monkeypatch.setenv("DSR_LITE_VARIANT", "16")       # not a kernel of the shipped build
+    monkeypatch.setenv("DSR_LITE_VARIANT", unknown)    # not a schedule of the library
     keep = []
     ins = (L.ObjectIn * 2)()
     for i, ob in enumerate(objs):

@@ -4,7 +4,7 @@ order, so every lite value, and with it every class, count and record, is bitwis
 
 The batch API hands out no copy of a batch's `dense` buffer, so the lite values themselves are
 compared where the library does expose them: the mesher's sign pass runs the same kernel
-(lite_kernel()) over a grid and dsr_mesher_peek returns its output.  The batch cases compare the
+(lite_schedule()) over a grid and dsr_mesher_peek returns its output.  The batch cases compare the
 records and the counters that depend on the lite values only (samples decoded, band and audit
 samples, the largest observed |lite - exact|).
 """

@@ -849,13 +849,14 @@ def test_refine_stops_at_ray_termination(gpu_decoder, monkeypatch):
 
 @pytest.mark.gpu
 def test_lite_staggered_groups_bitwise(gpu_decoder, monkeypatch):
-    """The staggered-group lite kernel (default DSR_LITE_VARIANT=1496: LDS event counters
-    instead of block barriers, dsr_mlp_lite.hpp: k_mlp_fwd_lite_st) gives the same lite values
+    """The staggered-group lite kernel (DSR_LITE_VARIANT=1496, the schedule before the default
+    3544's pinned B ring: LDS event counters instead of block barriers, dsr_mlp_lite.hpp:
+    k_mlp_fwd_lite_st) gives the same lite values
     whatever the stagger lag (0: B may start each GEMM at once, 7: half a GEMM behind) — a
     race on the LDS image would change values, classes and counts — and equals the unswizzled
     variant 472 bitwise; no block's bounded event wait expires (dsr_stats.lite_broken_blocks).
-    (Round 2 tested the scaled-epilogue variant 216 against the barrier kernel 88 here; 216
-    is no longer in the shipped library)"""
+    (Round 2 tested the scaled-epilogue variant 216 against the barrier kernel 88 here; both
+    have been removed)"""
     import ctypes
 
     import bench

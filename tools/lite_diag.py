@@ -5,7 +5,8 @@ For each (variant, lag, object groups) configuration: run the 8-object KITTI bat
 times and print, per run, the output hash, dsr_stats.lite_broken_blocks and — when a wait
 expired — the record of the first one (dsr_batch_lite_diag: workgroup, wave, the counter it
 waited on, target vs observed value, tile iteration, HW_ID / XCC_ID, and the real time its
-last polls took).  DESIGN.md §3.8 records that variant 216 broke with 2-4 object groups.
+last polls took).  DESIGN.md appendix A (L15) records that the removed variant 216 broke with
+2-4 object groups.
 """
 import ctypes
 import hashlib
@@ -28,10 +29,7 @@ reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 dec = decoder_from_state(S.make_decoder(1234), S.DEFAULT_SPECS)
 lib, ctx = dec.ctx.lib, dec.ctx
 os.environ["DSR_LITE"] = "1"
-# (216 needs a -DDSR_LITE_EXPERIMENTS build: DSR_LIB=<that .so> DSR_DIAG_216=1)
 configs = [("1496", "4", "4"), ("1496", "0", "4"), ("1496", "4", "2"), ("472", "4", "4")]
-if os.environ.get("DSR_DIAG_216") == "1":
-    configs += [("216", "0", "4"), ("216", "4", "4"), ("216", "0", "2"), ("216", "0", "1")]
 for v, lag, streams in configs:
     os.environ.update(DSR_LITE_VARIANT=v, DSR_LITE_LAG=lag, DSR_STREAMS=streams)
     for r in range(reps):

@@ -26,7 +26,7 @@ from deep_sdf.workspace import fold_state  # noqa: E402
 
 
 def lite_forward(layers, z, x):
-    """The lite kernel's arithmetic (dsr_mlp_lite.hpp, LV 1496) on samples x (n, 3)."""
+    """The lite kernel's arithmetic (dsr_mlp_lite.hpp, DSR_LITE_VARIANT 1496) on samples x (n, 3)."""
     W0, b0 = (np.asarray(a, np.float32) for a in layers[0])
     # lin0: code folded into the bias (fp32), xyz by fp32 fma in the kernel's order
     bias0 = (W0[:, :64].astype(np.float64) @ z.astype(np.float64) + b0).astype(np.float32)
