@@ -24,6 +24,7 @@
 #include "dsr_mc.hpp"
 #include "dsr_mesh.hpp"
 #include "dsr_render.hpp"
+#include "dsr_frame.hpp"
 
 #ifndef DSR_DEFAULT_FWD_VARIANT
 #define DSR_DEFAULT_FWD_VARIANT 12  // split-fp16 (3xFP16) + s_setprio (A/B: tools/fwd_variants.py)
@@ -329,6 +330,14 @@ struct dsr_batch {
   };
   std::vector<Stage> stage;
   hipEvent_t up_ev = nullptr;       // recorded after the last refill's uploads
+  // Frame refills (dsr_batch_refill_frame): one pinned block (depth | instance | detections) and
+  // one device block (the same, then the kernels' row tables and records; dsr_frame.hpp), grown to
+  // the largest frame seen and freed with the batch.  frame_n: detections of the last fill if it
+  // was a frame, else -1.
+  void* frame_host = nullptr;
+  void* frame_dev = nullptr;
+  size_t frame_host_bytes = 0, frame_dev_bytes = 0;
+  int frame_n = -1, frame_w = 0, frame_h = 0;
 };
 
 #define DSR_CHECK(ctx, call)                                                        \
@@ -1039,6 +1048,8 @@ int dsr_batch_destroy(dsr_batch* b) {
   if (b->graph) hipGraphExecDestroy(b->graph);
   for (auto& sg : b->stage)
     if (sg.host) hipHostFree(sg.host);
+  if (b->frame_host) hipHostFree(b->frame_host);
+  if (b->frame_dev) hipFree(b->frame_dev);
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (b->up_ev) ctx->ev_plain.push_back(b->up_ev);
   for (auto& e : b->ev)
@@ -1540,7 +1551,177 @@ int dsr_batch_refill(dsr_batch* b, int n_obj, const dsr_object_in* in) {
   if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
   DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
   b->n_active = n_obj;
+  b->frame_n = -1;
   b->ran = false;
+  return 0;
+}
+
+// ---- frame ingest (include/dsr.h; kernels and the host rule in dsr_frame.hpp)
+int dsr_frame_params_default(dsr_frame_params* p) {
+  if (!p) return -2;
+  p->max_pts = 250;
+  p->max_bg = 200;
+  p->downsample = 4;
+  p->expand = 5;
+  p->min_mask_area = 1000;
+  p->near = 0.01f;
+  p->far = INFINITY;
+  return 0;
+}
+
+static FrameCam frame_cam(const dsr_camera* cam) {
+  return FrameCam{cam->fx, cam->fy, cam->cx, cam->cy, cam->width, cam->height};
+}
+
+int dsr_frame_inputs_host(const dsr_camera* cam, const dsr_frame_params* params, const float* depth,
+                          const int* instance, int n_det, const dsr_frame_det* dets, float* pts, float* rays,
+                          float* dobs, dsr_frame_det_out* out) {
+  if (frame_args_error(cam, params, depth, instance, n_det, dets)) return -2;
+  frame_inputs_host_impl(frame_cam(cam), *params, depth, instance, n_det, dets, pts, rays, dobs, out);
+  return 0;
+}
+
+// the uploaded part of a frame block: depth | instance | detections, laid out as frame_carve does
+static void frame_pack(void* host, const dsr_camera* cam, const float* depth, const int* inst, int n_det,
+                       const dsr_frame_det* dets) {
+  const FrameDev H = frame_carve(host, cam->width, cam->height, n_det);
+  const size_t px = (size_t)cam->width * cam->height;
+  std::memcpy(H.depth, depth, px * sizeof(float));
+  std::memcpy(H.inst, inst, px * sizeof(int));
+  for (int d = 0; d < n_det; ++d) {
+    H.dets[d].label = dets[d].label;
+    for (int k = 0; k < 4; ++k) H.dets[d].bbox[k] = dets[d].bbox[k];
+  }
+}
+
+int dsr_frame_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params, const float* depth,
+                     const int* instance, int n_det, const dsr_frame_det* dets, float* pts, float* rays,
+                     float* dobs, dsr_frame_det_out* out) {
+  if (!ctx) return -2;
+  if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
+  if (n_det > 0 && (!pts || !rays || !dobs || !out)) return fail(ctx, "frame: null output arrays");
+  if (n_det == 0) return 0;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const int W = cam->width, H = cam->height;
+  const size_t up = frame_upload_bytes(W, H, n_det), all = frame_dev_bytes(W, H, n_det);
+  const size_t np = (size_t)n_det * params->max_pts * 3, nr = (size_t)n_det * ((size_t)params->max_pts + params->max_bg) * 3,
+               nz = (size_t)n_det * params->max_pts;
+  std::vector<char> host(up);
+  frame_pack(host.data(), cam, depth, instance, n_det, dets);
+  char* dev = nullptr;
+  float* o = nullptr;                            // pts | rays | dobs
+  hipStream_t s = ctx->stream;
+  int rc = 0;
+  auto chk = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == 0) {
+      ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+      rc = -1;
+    }
+    return e == hipSuccess;
+  };
+  if (chk(hipMalloc((void**)&dev, all), "hipMalloc (frame)") &&
+      chk(hipMalloc((void**)&o, sizeof(float) * (np + nr + nz)), "hipMalloc (frame outputs)")) {
+    const FrameDev D = frame_carve(dev, W, H, n_det);
+    // rows beyond a detection's counts come back as the caller had them
+    chk(hipMemcpyAsync(dev, host.data(), up, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o, pts, sizeof(float) * np, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o + np, rays, sizeof(float) * nr, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o + np + nr, dobs, sizeof(float) * nz, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    if (rc == 0) {
+      frame_launch(s, frame_cam(cam), *params, n_det, D, nullptr, o, o + np, o + np + nr);
+      chk(hipGetLastError(), "frame kernels");
+      chk(hipMemcpyAsync(pts, o, sizeof(float) * np, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(rays, o + np, sizeof(float) * nr, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(dobs, o + np + nr, sizeof(float) * nz, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(out, D.recs, sizeof(dsr_frame_det_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+    }
+    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
+  }
+  if (o) hipFree(o);
+  if (dev) hipFree(dev);
+  return rc;
+}
+
+int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                           const float* depth, const int* instance, int n_det, const dsr_frame_det* dets) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  if (!b->capacity) return fail(ctx, "dsr_batch_refill_frame needs a batch from dsr_batch_create_capacity");
+  if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
+  if (n_det > b->n_obj) return fail(ctx, "refill_frame: n_det exceeds the batch's object capacity");
+  if (params->max_pts > b->max_pts) return fail(ctx, "refill_frame: max_pts exceeds the batch's max_pts");
+  if ((long long)params->max_pts + params->max_bg > b->max_rays)
+    return fail(ctx, "refill_frame: max_pts + max_bg exceeds the batch's max_rays");
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  // the previous refill's copies read the staging buffers until they complete
+  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+  const int W = cam->width, H = cam->height;
+  const size_t up = frame_upload_bytes(W, H, n_det), all = frame_dev_bytes(W, H, n_det);
+  hipStream_t s = ctx->stream;
+  if (up > b->frame_host_bytes) {
+    if (b->frame_host) hipHostFree(b->frame_host);
+    b->frame_host = nullptr;
+    b->frame_host_bytes = 0;
+    DSR_CHECK(ctx, hipHostMalloc(&b->frame_host, up, hipHostMallocDefault));
+    b->frame_host_bytes = up;
+  }
+  if (all > b->frame_dev_bytes) {
+    // the kernels of an earlier frame refill may still read the old block
+    DSR_CHECK(ctx, hipStreamSynchronize(s));
+    if (b->frame_dev) hipFree(b->frame_dev);
+    b->frame_dev = nullptr;
+    b->frame_dev_bytes = 0;
+    DSR_CHECK(ctx, hipMalloc(&b->frame_dev, all));
+    b->frame_dev_bytes = all;
+  }
+  frame_pack(b->frame_host, cam, depth, instance, n_det, dets);
+  auto* desc = static_cast<ObjDesc*>(b->stage[0].host);
+  auto* t_in = static_cast<float*>(b->stage[1].host);
+  auto* z_in = static_cast<float*>(b->stage[2].host);
+  auto* is_oc = static_cast<int*>(b->stage[3].host);
+  for (int o = 0; o < b->n_obj; ++o) {
+    ObjDesc d = b->hdesc[o];                       // the slot's offsets; k_frame_scan writes the counts
+    d.n_pts = d.n_rays = d.n_fg = 0;
+    desc[o] = d;
+    const dsr_frame_det* x = o < n_det ? &dets[o] : nullptr;
+    float* t = t_in + (size_t)o * 16;
+    for (int i = 0; i < 16; ++i) t[i] = x ? x->t_cam_obj[i] : (i % 5 == 0 ? 1.f : 0.f);
+    float* z = z_in + (size_t)o * CODE;
+    std::memset(z, 0, sizeof(float) * CODE);
+    if (x && x->code) std::memcpy(z, x->code, sizeof(float) * b->dec->code_len);
+    is_oc[o] = (x && x->pose_is_obj_cam) ? 1 : 0;
+  }
+  for (int k = 0; k < 4; ++k)                      // desc, t_in, z_in, is_oc (pts / rays / dobs: the kernels)
+    DSR_CHECK(ctx, hipMemcpyAsync(b->stage[k].dev, b->stage[k].host, b->stage[k].bytes, hipMemcpyHostToDevice, s));
+  DSR_CHECK(ctx, hipMemcpyAsync(b->frame_dev, b->frame_host, up, hipMemcpyHostToDevice, s));
+  if (n_det > 0) {
+    frame_launch(s, frame_cam(cam), *params, n_det, frame_carve(b->frame_dev, W, H, n_det), b->desc, b->pts,
+                 b->rays, b->dobs);
+    DSR_CHECK(ctx, hipGetLastError());
+  }
+  if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
+  DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
+  b->n_active = n_det;
+  b->frame_n = n_det;
+  b->frame_w = W;
+  b->frame_h = H;
+  b->ran = false;
+  return 0;
+}
+
+int dsr_batch_frame_info(dsr_batch* b, dsr_frame_det_out* out) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  if (b->frame_n < 0) return fail(ctx, "dsr_batch_frame_info: the batch's last fill was not a frame (dsr_batch_refill_frame)");
+  if (b->frame_n == 0) return 0;
+  if (!out) return fail(ctx, "null argument");
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+  const FrameDev D = frame_carve(b->frame_dev, b->frame_w, b->frame_h, b->frame_n);
+  DSR_CHECK(ctx, hipMemcpy(out, D.recs, sizeof(dsr_frame_det_out) * b->frame_n, hipMemcpyDeviceToHost));
   return 0;
 }
 

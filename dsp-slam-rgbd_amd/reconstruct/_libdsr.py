@@ -152,6 +152,30 @@ class RenderStats(C.Structure):
 RENDER_OK, RENDER_OFFSCREEN, RENDER_SKIP_NEAR = 0, 1, 2   # include/dsr.h DSR_RENDER_*
 
 
+class FrameParams(C.Structure):
+    """dsr_frame_params: every value is taken literally (dsr_frame_params_default fills the defaults)."""
+    _fields_ = [("max_pts", C.c_int), ("max_bg", C.c_int), ("downsample", C.c_int), ("expand", C.c_int),
+                ("min_mask_area", C.c_int), ("near", C.c_float), ("far", C.c_float)]
+
+
+class FrameDet(C.Structure):
+    """dsr_frame_det: a label of the instance image, an optional box (bbox[2] < bbox[0]: the mask's
+    tight box) and the pose / code / pose_is_obj_cam of dsr_object_in."""
+    _fields_ = [("label", C.c_int), ("bbox", C.c_int * 4), ("t_cam_obj", C.c_float * 16), ("code", FP),
+                ("pose_is_obj_cam", C.c_int)]
+
+
+class FrameDetOut(C.Structure):
+    """dsr_frame_det_out: the ingest record of one detection."""
+    _fields_ = [("status", C.c_int), ("n_mask", C.c_int), ("n_valid", C.c_int), ("n_pts", C.c_int),
+                ("n_bg", C.c_int), ("box", C.c_int * 4), ("grid_h", C.c_int), ("grid_w", C.c_int)]
+
+
+FRAME_OK, FRAME_NO_MASK, FRAME_SMALL_MASK, FRAME_NO_DEPTH = 0, 1, 2, 3   # include/dsr.h DSR_FRAME_*
+FRAME_STATUS = {0: "ok", 1: "no pixel carries the label", 2: "mask of at most min_mask_area pixels",
+                3: "no valid depth in the mask"}
+
+
 #: dsr_batch_lite_diag record layout (csrc/dsr_dev.hpp: STD_*)
 LITE_DIAG_FIELDS = ("broken_blocks", "recorded", "block", "wave", "counter", "target", "observed", "tile_iter",
                     "hw_id", "xcc_id", "polls", "real_ticks")
@@ -215,12 +239,21 @@ SIGNATURES = {
     "dsr_renderer_stats_get": (C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
     "dsr_renderer_destroy": (C.c_int, [C.c_void_p]),
     "dsr_render_layout": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_int, C.POINTER(RenderObject), IP, IP]),
+    "dsr_frame_params_default": (C.c_int, [C.POINTER(FrameParams)]),
+    "dsr_frame_inputs_host": (C.c_int, [C.POINTER(Camera), C.POINTER(FrameParams), FP, IP, C.c_int,
+                                        C.POINTER(FrameDet), FP, FP, FP, C.POINTER(FrameDetOut)]),
+    "dsr_frame_inputs": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams), FP, IP, C.c_int,
+                                   C.POINTER(FrameDet), FP, FP, FP, C.POINTER(FrameDetOut)]),
+    "dsr_batch_refill_frame": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams), FP, IP, C.c_int,
+                                         C.POINTER(FrameDet)]),
+    "dsr_batch_frame_info": (C.c_int, [C.c_void_p, C.POINTER(FrameDetOut)]),
 }
 
 #: entry points added without an ABI number change: callers detect them by the symbol, so a
 #: library of the same ABI number built before them still loads (A/B runs under DSR_LIB)
 BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_render", "dsr_renderer_stats_get",
-             "dsr_renderer_destroy", "dsr_render_layout")
+             "dsr_renderer_destroy", "dsr_render_layout", "dsr_frame_params_default", "dsr_frame_inputs_host",
+             "dsr_frame_inputs", "dsr_batch_refill_frame", "dsr_batch_frame_info")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

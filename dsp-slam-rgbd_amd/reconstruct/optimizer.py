@@ -15,6 +15,9 @@ runs in libdsr's HIP kernels on an MI355X (``include/dsr.h``):
 * ``Optimizer.reconstruct_objects_views([...])`` / ``reconstruct_object_views`` — NEW: one
   code and one pose per object fitted to the pooled residuals of several keyframes' views
   -> ``dsr_reconstruct_views``.
+* ``Optimizer.reconstruct_frame(depth, instance, detections, camera)`` — NEW: a keyframe straight
+  from a depth image and an instance-label image; device kernels build every detection's points
+  and rays in the slots of a capacity batch -> ``dsr_batch_refill_frame``.
 * ``Optimizer.compute_sdf_loss_objectpoint_zhjd(pts_obj, code)`` —
   optimizer.py:207-213 -> ``dsr_sdf_eval``.
 * ``Optimizer.estimate_pose_cam_obj(...)`` — optimizer.py:46-87 -> ``dsr_pose_only``.
@@ -259,7 +262,10 @@ class Optimizer(object):
         :class:`MeshExtractor`) the good objects are meshed by one batch call
         (LocalMapping_util.cc:197, 429 mesh every successful reconstruction) and every result
         carries ``vertices`` / ``faces`` (``None`` for a failed object)."""
-        res = self.reconstruct_keyframe_async(detections).wait()
+        return self._mesh_results(self.reconstruct_keyframe_async(detections).wait(), mesher)
+
+    @staticmethod
+    def _mesh_results(res, mesher):
         if mesher is None:
             return res
         good = [i for i, r in enumerate(res) if r["is_good"]]
@@ -269,6 +275,72 @@ class Optimizer(object):
         for i, mesh in zip(good, meshes):
             res[i]["vertices"], res[i]["faces"] = mesh.vertices, mesh.faces
         return res
+
+    def reconstruct_frame(self, depth, instance, detections, camera, mesher=None, **params):
+        """One keyframe straight from a depth image and an instance-label image (the format
+        ``SdfRenderer.render`` emits): what ``reconstruct_keyframe`` returns for the inputs
+        ``reconstruct.utils.frame_inputs`` builds, without building them on the host.  The images
+        are uploaded once and device kernels fill the slots of a fixed-capacity batch
+        (dsr_batch_refill_frame; the rule is DESIGN.md §3.5b, replacing get_detections /
+        pixels_sampler / get_rays, kitti_sequence.py:70-92, mono_sequence.py:51-73,
+        loss_utils.py:23-37).  ``detections``: dicts ``{label, t_cam_obj, code=None, bbox=None,
+        reconstructed=True}``; for ``reconstructed=False`` the flipped hypothesis
+        (``t_cam_obj @ diag(-1, 1, -1, 1)``, same label, so the same pixels) joins the batch and
+        the choice between the two is ``KeyframeHandle``'s.  ``camera``: ``utils.frame_camera``;
+        ``params``: ``utils.FRAME_PARAM_NAMES`` (the slot's capacity comes from max_pts / max_bg).
+        Every result carries the detection's ingest record as ``ingest``.  With ``keyframe_mode``
+        "oneshot", or when no slot is within the capacity bounds, the inputs are built on the host
+        (``frame_inputs``) and run through ``reconstruct_keyframe``."""
+        from reconstruct import utils as U
+
+        cam = U.frame_camera(camera)
+        p = U.frame_params(**params)
+        depth, instance = U.frame_images(depth, instance, cam)
+        hyp, pairs = [], []
+        for det in detections:
+            i, j = len(hyp), None
+            hyp.append(det)
+            if not det.get("reconstructed", True):
+                j = len(hyp)
+                hyp.append(dict(det, t_cam_obj=np.asarray(det["t_cam_obj"], np.float32).reshape(4, 4) @ FLIP))
+            pairs.append((i, j))
+        n = len(hyp)
+        if n == 0:
+            return []
+        ctx = self._ctx
+        slot = None
+        if hasattr(ctx.lib, "dsr_batch_refill_frame") and p.max_pts >= 1 and p.max_bg >= 0:
+            slot = self._slot_for_caps(n, p.max_pts, p.max_pts + p.max_bg, n * (p.max_pts + p.max_bg))
+        if slot is None:
+            objects, records = U.frame_inputs(depth, instance, detections, cam, **params)
+            res = self.reconstruct_keyframe([ob + (det.get("reconstructed", True),)
+                                             for ob, det in zip(objects, detections)], mesher)
+            for r, rec in zip(res, records):
+                r["ingest"] = rec
+            return res
+        dets, keep = U.frame_dets(hyp, self.code_len)
+        outs = (L.ObjectOut * n)()
+        recs = (L.FrameDetOut * n)()
+        ctx.check(ctx.lib.dsr_batch_refill_frame(slot.handle, cam, p, L.fptr(depth), L.iptr(instance), n, dets),
+                  "dsr_batch_refill_frame")
+        slot.busy = True
+        try:
+            ctx.check(ctx.lib.dsr_batch_run(slot.handle), "dsr_batch_run")
+            ctx.check(ctx.lib.dsr_batch_download(slot.handle, outs), "dsr_batch_download")
+            ctx.check(ctx.lib.dsr_batch_frame_info(slot.handle, recs), "dsr_batch_frame_info")
+        finally:
+            slot.busy = False
+        res = []
+        for i, j in pairs:
+            k = i
+            if j is not None and float(outs[i].loss) > float(outs[j].loss):
+                k = j
+            r = self._result(outs[k], self.code_len)
+            r["iters_done"] = int(outs[k].iters_done)
+            r["fail_reason"] = L.FAIL_REASONS.get(int(outs[k].fail_reason), "?")
+            r["ingest"] = U.frame_record(recs[k])
+            res.append(r)
+        return self._mesh_results(res, mesher)
 
     MAX_SLOTS = 4
     # A slot batch is laid out for max_obj x max_rays x M ray samples whatever the fill, and every
@@ -296,11 +368,14 @@ class Optimizer(object):
         keyframe no longer destroys a large free slot and its captured graph)."""
         if self.keyframe_mode not in ("slot", "graph") or not objects:
             return None
-        n = len(objects)
         rays = [_f32(ob[2], 3).shape[0] for ob in objects]
-        need_p = max(_f32(ob[1], 3).shape[0] for ob in objects)
-        need_r = max(rays)
-        real = sum(rays)
+        return self._slot_for_caps(len(objects), max(_f32(ob[1], 3).shape[0] for ob in objects), max(rays), sum(rays))
+
+    def _slot_for_caps(self, n, need_p, need_r, real):
+        """``_slot_for`` by numbers: ``n`` objects of at most ``need_p`` points and ``need_r`` rays,
+        ``real`` rays in all."""
+        if self.keyframe_mode not in ("slot", "graph") or n <= 0:
+            return None
         graph = self.keyframe_mode == "graph"
         self._slot_tick = getattr(self, "_slot_tick", 0) + 1
         free = [sl for sl in self._slots if not sl.busy and sl.graph == graph]

@@ -117,6 +117,122 @@ def views_from_world(t_cam_world_list):
     return [np.eye(4)] + [t @ inv0 for t in ts[1:]]
 
 
+FRAME_PARAM_NAMES = ("max_pts", "max_bg", "downsample", "expand", "min_mask_area", "near", "far")
+
+
+def frame_params(**params):
+    """``dsr_frame_params``: the library's defaults (dsr_frame_params_default: max_pts 250, max_bg
+    200, downsample 4, expand 5, min_mask_area 1000, near 0.01, far +inf) with ``params`` on top."""
+    from reconstruct import _libdsr as L
+
+    unknown = set(params) - set(FRAME_PARAM_NAMES)
+    if unknown:
+        raise TypeError(f"unknown frame parameters: {sorted(unknown)}")
+    p = L.FrameParams()
+    if L.load_library().dsr_frame_params_default(p) != 0:
+        raise L.DsrError("dsr_frame_params_default failed")
+    for k, v in params.items():
+        setattr(p, k, float(v) if k in ("near", "far") else int(v))
+    return p
+
+
+def frame_camera(camera):
+    """``dsr_camera`` from a ``_libdsr.Camera``, a dict or an object with width, height, fx, fy, cx,
+    cy, or that 6-tuple."""
+    from reconstruct import _libdsr as L
+
+    if isinstance(camera, L.Camera):
+        return camera
+    names = ("width", "height", "fx", "fy", "cx", "cy")
+    if isinstance(camera, dict):
+        v = [camera[k] for k in names]
+    elif hasattr(camera, "fx"):
+        v = [getattr(camera, k) for k in names]
+    else:
+        v = list(camera)
+    return L.Camera(int(v[0]), int(v[1]), float(v[2]), float(v[3]), float(v[4]), float(v[5]))
+
+
+def frame_dets(detections, code_len=64):
+    """The ``dsr_frame_det`` array of a list of detection dicts ``{label, t_cam_obj, code=None,
+    bbox=None, reconstructed=True}`` (``reconstructed`` is the caller's business), and the arrays
+    it points into."""
+    from reconstruct import _libdsr as L
+
+    n = len(detections)
+    dets = (L.FrameDet * max(n, 1))()
+    keep = []
+    for i, det in enumerate(detections):
+        dets[i].label = int(det["label"])
+        bbox = det.get("bbox")
+        dets[i].bbox[:] = [0, 0, -1, -1] if bbox is None else [int(x) for x in bbox]
+        dets[i].t_cam_obj[:] = np.asarray(det["t_cam_obj"], np.float32).reshape(16).tolist()
+        code = det.get("code")
+        if code is not None:
+            c = np.ascontiguousarray(np.asarray(code, np.float32).reshape(-1)[:code_len])
+            if c.shape[0] != code_len:
+                raise ValueError(f"code must hold at least {code_len} values, got {c.shape[0]}")
+            keep.append(c)
+            dets[i].code = L.fptr(c)
+        dets[i].pose_is_obj_cam = 0
+    return dets, keep
+
+
+def frame_record(o):
+    """A ``dsr_frame_det_out`` as a dict."""
+    return ForceKeyErrorDict(status=int(o.status), n_mask=int(o.n_mask), n_valid=int(o.n_valid),
+                             n_pts=int(o.n_pts), n_bg=int(o.n_bg), box=tuple(o.box), grid_h=int(o.grid_h),
+                             grid_w=int(o.grid_w))
+
+
+def frame_images(depth, instance, camera):
+    """depth / instance as contiguous (height, width) float32 / int32 arrays of the camera's size."""
+    depth = np.ascontiguousarray(np.asarray(depth), dtype=np.float32)
+    instance = np.ascontiguousarray(np.asarray(instance), dtype=np.int32)
+    shape = (camera.height, camera.width)
+    if depth.shape != shape or instance.shape != shape:
+        raise ValueError(f"depth {depth.shape} / instance {instance.shape} must be (height, width) = {shape}")
+    return depth, instance
+
+
+def frame_inputs(depth, instance, detections, camera, **params):
+    """What the reference builds per detection on the CPU — ``FrameWithLiDAR.get_detections`` +
+    ``pixels_sampler`` (kitti_sequence.py:70-92, :139-146, :200-210), ``Frame.pixels_sampler``
+    (mono_sequence.py:51-73) and ``get_rays`` (loss_utils.py:23-37) — from a depth image and an
+    instance-label image, by the exact rule of DESIGN.md §3.5b (``dsr_frame_inputs_host``: plain
+    C++ on the host, no device).  ``detections``: dicts ``{label, t_cam_obj, code=None, bbox=None,
+    reconstructed=True}``; ``camera``: see ``frame_camera``; ``params``: ``FRAME_PARAM_NAMES``.
+    Returns ``(objects, records)``: per detection ``(t_cam_obj, pts, rays, depth, code)`` trimmed to
+    its counts — the tuple ``Optimizer.reconstruct_objects`` takes — and its ingest record
+    (``frame_record``).  A detection that is not ok has empty arrays."""
+    from reconstruct import _libdsr as L
+
+    lib = L.load_library()
+    cam = frame_camera(camera)
+    p = frame_params(**params)
+    depth, instance = frame_images(depth, instance, cam)
+    n = len(detections)
+    dets, keep = frame_dets(detections)
+    mp, mr = max(p.max_pts, 0), max(p.max_pts, 0) + max(p.max_bg, 0)
+    pts = np.zeros((max(n, 1), mp, 3), np.float32)
+    rays = np.zeros((max(n, 1), mr, 3), np.float32)
+    dobs = np.zeros((max(n, 1), mp), np.float32)
+    out = (L.FrameDetOut * max(n, 1))()
+    rc = lib.dsr_frame_inputs_host(cam, p, L.fptr(depth), L.iptr(instance), n, dets, L.fptr(pts), L.fptr(rays),
+                                   L.fptr(dobs), out)
+    if rc != 0:
+        raise L.DsrError(f"dsr_frame_inputs_host failed ({rc}): bad camera, image or frame parameters")
+    objects, records = [], []
+    for i, det in enumerate(detections):
+        r = frame_record(out[i])
+        code = det.get("code")
+        objects.append((np.asarray(det["t_cam_obj"], np.float32).reshape(4, 4), pts[i, :r.n_pts].copy(),
+                        rays[i, :r.n_pts + r.n_bg].copy(), dobs[i, :r.n_pts].copy(),
+                        None if code is None else np.asarray(code, np.float32)))
+        records.append(r)
+    return objects, records
+
+
 def create_voxel_grid(vol_dim=128):
     """utils.py:97-116.  Note the reference's ``LongTensor / vol_dim`` is TRUE division
     in torch >= 1.6 (fp32), so its x/y columns are not integer lattice indices; this

@@ -473,6 +473,98 @@ int dsr_renderer_destroy(dsr_renderer* r);
 int dsr_render_layout(const dsr_camera* cam, float near, int n_obj, const dsr_render_object* objs,
                       int* rect, int* status);
 
+/* ---- frame ingest: one depth image + one instance-label image + a list of detections -> every
+ * detection's surface points, rays and observed depths (the dsr_object_in arrays), on the host or
+ * straight into the slots of a capacity batch on the device.  Replaces the per-detection numpy of
+ * FrameWithLiDAR.get_detections + pixels_sampler (reconstruct/kitti_sequence.py:70-92, :139-146,
+ * :200-210), Frame.pixels_sampler (reconstruct/mono_sequence.py:51-73) and get_rays
+ * (reconstruct/loss_utils.py:23-37) for the RGB-D case: the images are what dsr_renderer_render
+ * emits.  DESIGN.md 3.5b states the rule exactly; callers detect these entry points by symbol, the
+ * ABI number is unchanged.  Out of scope: the occlusion masks of kitti_sequence.py:177-216 and
+ * lens distortion (the camera is dsr_camera: pinhole, zero skew, no distortion).
+ *
+ * Per detection: mask pixels are those with instance == label, valid pixels the mask pixels with
+ * z == z && z > near && z < far, both in row-major order.  sel(i, n, N) = (i (N-1)) / (n-1) in
+ * 64-bit integers (0 for n = 1), applied only when N > n — np.linspace(0, N-1, n).astype(int32)
+ * made exact (the integer rule is the specification; the float idiom differs from it where fp64
+ * i * step lands just below an integer).  n_pts = n_fg = min(n_valid, max_pts); surface point and
+ * foreground ray i come from valid pixel sel(i, max_pts, n_valid) = (u, v) of depth z: in fp32,
+ * one correctly rounded operation each, rx = ((float)u - cx) / fx, ry = ((float)v - cy) / fy, ray
+ * (rx, ry, 1), point (rx z, ry z, z), observed depth z — the pixel convention of dsr_camera, not
+ * bitwise get_rays' fp64 inverse-K product.  Background rays (pixels_sampler): the box (l, t, r, b),
+ * inclusive, is bbox clamped to the image when bbox[2] >= bbox[0], else the tight box of the mask;
+ * it grows by `expand` (l = l > e ? l - e : 0, r = r < W-1-e ? r + e : W-1, the same for t, b); the
+ * grid has gh = (b-t+1) / downsample rows t + sel(j, gh, b-t+1) and gw = (r-l+1) / downsample
+ * columns l + sel(k, gw, r-l+1); its pixels in (j, k) order with instance != label are the N_bg
+ * candidates, of which min(N_bg, max_bg) are kept by sel(i, max_bg, N_bg).  Rays are laid out
+ * foreground first; background rays have observed depth 0 (as dsr_batch_refill).  Two detections
+ * may carry the same label (the flipped hypothesis of LocalMapping_util.cc:400-410): they get the
+ * same pixels.  A detection that is not DSR_FRAME_OK yields an empty object (no points, no rays:
+ * the reference's numeric failure). */
+typedef struct {
+  int max_pts;                    /* surface points = foreground rays kept per detection (250) */
+  int max_bg;                     /* background rays kept per detection (200) */
+  int downsample;                 /* background grid stride (4) */
+  int expand;                     /* box growth in pixels (5) */
+  int min_mask_area;              /* masks of at most this many pixels are skipped (1000) */
+  float near, far;                /* valid depth is near < z < far (0.01, +inf) */
+} dsr_frame_params;
+typedef struct {
+  int label;                      /* the detection's value in the instance image */
+  int bbox[4];                    /* l, t, r, b inclusive; bbox[2] < bbox[0]: the mask's tight box */
+  float t_cam_obj[16];            /* as dsr_object_in */
+  const float* code;              /* as dsr_object_in: (code_len,) or NULL */
+  int pose_is_obj_cam;            /* as dsr_object_in */
+} dsr_frame_det;
+enum {
+  DSR_FRAME_OK = 0,
+  DSR_FRAME_NO_MASK = 1,          /* no pixel carries the label */
+  DSR_FRAME_SMALL_MASK = 2,       /* n_mask <= min_mask_area (kitti_sequence.py:200) */
+  DSR_FRAME_NO_DEPTH = 3          /* n_valid == 0 */
+};
+typedef struct {
+  int status;                     /* DSR_FRAME_* */
+  int n_mask, n_valid;
+  int n_pts, n_bg;                /* rows written: n_pts points / depths, n_pts + n_bg rays (0 unless OK) */
+  int box[4];                     /* the expanded box; 0, 0, -1, -1 when there is none (no mask and
+                                     no given box, or a given box that misses the image) */
+  int grid_h, grid_w;             /* gh, gw of that box (0 without one) */
+} dsr_frame_det_out;
+
+/* Host only: max_pts 250, max_bg 200, downsample 4, expand 5, min_mask_area 1000, near 0.01,
+ * far +inf (the reference's sampler settings, kitti_sequence.py:70-92 / mono_sequence.py:51-73).
+ * The other calls take every value literally: there is no "0 means default". */
+int dsr_frame_params_default(dsr_frame_params* p);
+/* The rule in plain C++ on the host — no context, no device (replaces get_detections /
+ * pixels_sampler / get_rays, kitti_sequence.py:70-92, mono_sequence.py:51-73, loss_utils.py:23-37).
+ * depth, instance: height x width.  Fixed strides per detection: pts max_pts x 3, rays
+ * (max_pts + max_bg) x 3, dobs max_pts; rows beyond a detection's counts are left untouched; out:
+ * n_det records.  Returns < 0 (no message: there is no context) for null images, a non-positive
+ * image size or focal length, max_pts < 1, max_bg < 0, downsample < 1, expand < 0, n_det < 0. */
+int dsr_frame_inputs_host(const dsr_camera* cam, const dsr_frame_params* params, const float* depth,
+                          const int* instance, int n_det, const dsr_frame_det* dets, float* pts, float* rays,
+                          float* dobs, dsr_frame_det_out* out);
+/* The same arrays and records produced by the device kernels (k_frame_*, csrc/dsr_frame.hpp) and
+ * copied back: bitwise those of dsr_frame_inputs_host (pixels_sampler / get_rays as above). */
+int dsr_frame_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params, const float* depth,
+                     const int* instance, int n_det, const dsr_frame_det* dets, float* pts, float* rays,
+                     float* dobs, dsr_frame_det_out* out);
+/* dsr_batch_refill from a frame (get_detections, kitti_sequence.py:139-146, without the host
+ * arrays): the images go through pinned staging onto the context stream, ordered after the
+ * previous run; the kernels write slot i's pts / rays / dobs rows and its counts in device memory
+ * for detection i; poses, codes and pose_is_obj_cam are taken as dsr_batch_refill takes them;
+ * slots >= n_det are empty.  No kernel argument of the run changes, so a DSR_BATCH_GRAPH graph
+ * stays valid.  Errors, returned before the device is touched: a batch that is not a capacity
+ * batch, n_det above its slot count, max_pts above its max_pts, max_pts + max_bg above its
+ * max_rays, and the argument errors of dsr_frame_inputs_host.  The image buffers grow with the
+ * image size, belong to the batch and are freed with it. */
+int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                           const float* depth, const int* instance, int n_det, const dsr_frame_det* dets);
+/* Waits for the last dsr_batch_refill_frame and copies its n_det records (the ingest outcome
+ * get_detections reports by dropping detections, kitti_sequence.py:200-210); an error when the
+ * batch's last fill was not a frame. */
+int dsr_batch_frame_info(dsr_batch* b, dsr_frame_det_out* out);
+
 /* ---- multi-GPU from one process: replaces the per-detection loop
  * LocalMapping_util.cc:165-206 spread over devices.  ctx[g] / dec[g] are one context and
  * its decoder per device; objects are LPT-partitioned (cost n_rays*M + n_pts), each
