@@ -24,6 +24,7 @@
 #include "dsr_mc.hpp"
 #include "dsr_mesh.hpp"
 #include "dsr_render.hpp"
+#include "dsr_scene.hpp"
 #include "dsr_frame.hpp"
 
 #ifndef DSR_DEFAULT_FWD_VARIANT
@@ -3624,6 +3625,394 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
       o.n_unconverged = hcnt[(size_t)i * RC_INTS + RC_UNCONV];
       o.n_visible = hcnt[(size_t)i * RC_INTS + RC_VISIBLE];
     }
+  return 0;
+}
+
+// ---- scene SDF queries (kernels: dsr_scene.hpp) -------------------------------
+constexpr int SCENE_PASS_OBJ = 64;                    // objects per pass at most (bounds the tile padding)
+constexpr size_t SCENE_MIN_PAIRS = (size_t)1 << 22;   // pair slots of the pass buffers at least
+constexpr int SCENE_MAX_PTS = 1 << 24;
+
+struct dsr_scene {
+  dsr_ctx* ctx = nullptr;
+  const dsr_decoder* dec = nullptr;
+  int max_obj = 0, max_pts = 0;
+  size_t cap = 0;                    // pair slots: max(max_pts, SCENE_MIN_PAIRS)
+  int max_chunks = 0, max_tiles = 0; // of one pass
+  std::vector<void*> allocs;
+  // per object (max_obj)
+  SceneObj* objs = nullptr;
+  ObjDesc* desc = nullptr;
+  float *codes = nullptr, *b0 = nullptr, *b4 = nullptr;
+  int *ocount = nullptr, *otile = nullptr, *wcount = nullptr, *wtile = nullptr, *nwin = nullptr;
+  SceneSums* sums = nullptr;
+  // per point (max_pts)
+  float* pts = nullptr;
+  unsigned long long* keys = nullptr;
+  float* dist = nullptr;
+  int* obj = nullptr;
+  // per pass
+  float4* cand = nullptr;
+  float* dense = nullptr;
+  int *ccnt = nullptr, *gpos = nullptr, *ntiles = nullptr;
+  Tile* tiles = nullptr;
+  ScenePart* part = nullptr;
+  // gradient: allocated at the first query that asks for it
+  float *grad = nullptr, *raw = nullptr;
+  float4* gcand = nullptr;           // max_pts + 64 * SCENE_PASS_OBJ (tiles padded per object)
+  hipEvent_t ev[4] = {};
+  std::vector<SceneObj> hobjs;       // the objects of dsr_scene_set_objects
+  std::vector<ObjDesc> hdesc;
+  int n_obj = -1;                    // -1: before dsr_scene_set_objects
+  int q_obj = -1, q_pts = 0;         // the last query's objects and points (-1: none)
+  int held0 = 0, held_k = 0;         // the objects whose candidates the pass buffers hold
+  std::vector<int> q_in;             // the last query's n_in
+  dsr_scene_stats st{};
+};
+
+static bool scene_alloc(dsr_scene* sc, void** p, size_t bytes) {
+  if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  sc->allocs.push_back(*p);
+  return true;
+}
+
+// One object's pose for the query: T_ow = inverse(t_world_obj) in fp64 (adjugate / determinant, as
+// render_pose), rounded once; s = det(R)^(1/3) rounded once.  false: a non-finite entry, a last
+// row that is not 0 0 0 1, or det <= 0.
+static bool scene_pose(const float* t, SceneObj* o) {
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(t[i])) return false;
+  RenderPose P;
+  if (!render_pose(t, &P)) return false;
+  std::memcpy(o->T, P.Toc, sizeof(o->T));
+  o->s = (float)P.rho;
+  o->pad[0] = o->pad[1] = o->pad[2] = 0;
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(o->T[i])) return false;
+  return std::isfinite(o->s) && o->s > 0.f;
+}
+
+// the pair rule on the host: the same fused operations as sc_point / sc_in_ball (dsr_scene.hpp)
+static bool scene_pair_host(const SceneObj& o, const float* p, float* x) {
+  for (int k = 0; k < 3; ++k)
+    x[k] = std::fmaf(o.T[k * 4], p[0], std::fmaf(o.T[k * 4 + 1], p[1], std::fmaf(o.T[k * 4 + 2], p[2], o.T[k * 4 + 3])));
+  const float r2 = std::fmaf(x[0], x[0], std::fmaf(x[1], x[1], x[2] * x[2]));
+  return r2 < 1.0f;
+}
+
+int dsr_scene_bin_host(int n_obj, const dsr_scene_object* objs, int n_pts, const float* pts_world, int obj,
+                       int cap, int* idx, float* x_obj, int* n_in, float* scale) {
+  if (n_obj <= 0 || !objs || n_pts < 0 || (n_pts > 0 && !pts_world) || obj < 0 || obj >= n_obj || cap < 0) return -2;
+  SceneObj o;
+  for (int i = 0; i < n_obj; ++i)
+    if (!scene_pose(objs[i].t_world_obj, &o)) return -2;
+  scene_pose(objs[obj].t_world_obj, &o);
+  if (scale) *scale = o.s;
+  int n = 0;
+  for (int p = 0; p < n_pts; ++p) {
+    float x[3];
+    if (scene_pair_host(o, pts_world + (size_t)p * 3, x)) n += 1;
+  }
+  if (n_in) *n_in = n;
+  if (n > cap) return -5;
+  n = 0;
+  for (int p = 0; p < n_pts; ++p) {
+    float x[3];
+    if (!scene_pair_host(o, pts_world + (size_t)p * 3, x)) continue;
+    if (idx) idx[n] = p;
+    if (x_obj) std::memcpy(x_obj + (size_t)n * 3, x, sizeof(x));
+    n += 1;
+  }
+  return 0;
+}
+
+int dsr_scene_destroy(dsr_scene* sc) {
+  if (!sc) return 0;
+  hipSetDevice(sc->ctx->device);
+  hipStreamSynchronize(sc->ctx->stream);
+  for (hipEvent_t e : sc->ev)
+    if (e) hipEventDestroy(e);
+  for (void* p : sc->allocs) hipFree(p);
+  delete sc;
+  return 0;
+}
+
+int dsr_scene_create(dsr_ctx* ctx, const dsr_decoder* dec, int max_obj, int max_pts, dsr_scene** out) {
+  if (!ctx || !dec || !out) return fail(ctx, "null argument");
+  *out = nullptr;
+  if (max_obj < 1) return fail(ctx, "max_obj must be >= 1");
+  if (max_pts < 1 || max_pts > SCENE_MAX_PTS) return fail(ctx, "max_pts must be in [1, 2^24]");
+  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  hipSetDevice(ctx->device);
+  auto* sc = new dsr_scene();
+  sc->ctx = ctx;
+  sc->dec = dec;
+  sc->max_obj = max_obj;
+  sc->max_pts = max_pts;
+  sc->cap = std::max((size_t)max_pts, SCENE_MIN_PAIRS);
+  sc->max_chunks = (int)(sc->cap / SCHUNK) + SCENE_PASS_OBJ;
+  sc->max_tiles = (int)(sc->cap / TILE) + SCENE_PASS_OBJ;
+  sc->hdesc.assign(max_obj, ObjDesc{});
+  const size_t no = (size_t)max_obj, np = (size_t)max_pts, cap = sc->cap;
+  auto A = [&](void** p, size_t bytes) { return scene_alloc(sc, p, bytes); };
+  bool ok = A((void**)&sc->objs, sizeof(SceneObj) * no) && A((void**)&sc->desc, sizeof(ObjDesc) * no) &&
+            A((void**)&sc->codes, sizeof(float) * CODE * no) && A((void**)&sc->b0, sizeof(float) * HID * no) &&
+            A((void**)&sc->b4, sizeof(float) * HID * no) && A((void**)&sc->ocount, sizeof(int) * no) &&
+            A((void**)&sc->otile, sizeof(int) * no) && A((void**)&sc->wcount, sizeof(int) * no) &&
+            A((void**)&sc->wtile, sizeof(int) * no) && A((void**)&sc->nwin, sizeof(int) * no) &&
+            A((void**)&sc->sums, sizeof(SceneSums) * no) && A((void**)&sc->pts, sizeof(float) * 3 * np) &&
+            A((void**)&sc->keys, sizeof(unsigned long long) * np) && A((void**)&sc->dist, sizeof(float) * np) &&
+            A((void**)&sc->obj, sizeof(int) * np) && A((void**)&sc->cand, sizeof(float4) * cap) &&
+            A((void**)&sc->dense, sizeof(float) * cap) && A((void**)&sc->ccnt, sizeof(int) * sc->max_chunks) &&
+            A((void**)&sc->gpos, sizeof(int) * sc->max_chunks) && A((void**)&sc->ntiles, sizeof(int)) &&
+            A((void**)&sc->tiles, sizeof(Tile) * sc->max_tiles) && A((void**)&sc->part, sizeof(ScenePart) * sc->max_tiles);
+  for (hipEvent_t& e : sc->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    dsr_scene_destroy(sc);
+    return fail(ctx, "hipMalloc failed (scene)");
+  }
+  *out = sc;
+  return 0;
+}
+
+int dsr_scene_stats_get(const dsr_scene* sc, dsr_scene_stats* st) {
+  if (!sc || !st) return -2;
+  *st = sc->st;
+  return 0;
+}
+
+int dsr_scene_set_objects(dsr_scene* sc, int n_obj, const dsr_scene_object* in) {
+  if (!sc) return -2;
+  dsr_ctx* ctx = sc->ctx;
+  if (n_obj > 0 && !in) return fail(ctx, "null argument");
+  if (n_obj < 0 || n_obj > sc->max_obj) return fail(ctx, "n_obj must be in [0, max_obj]");
+  const dsr_decoder* dec = sc->dec;
+  std::vector<SceneObj> ho(n_obj);
+  std::vector<float> hz((size_t)n_obj * CODE, 0.f);
+  for (int i = 0; i < n_obj; ++i) {
+    if (!in[i].code) return fail(ctx, "null argument (code)");
+    if (!scene_pose(in[i].t_world_obj, &ho[i]))
+      return fail(ctx, "t_world_obj must be finite with the last row 0 0 0 1 and a positive determinant (object " +
+                           std::to_string(i) + ")");
+    for (int k = 0; k < dec->code_len; ++k)
+      if (!std::isfinite(in[i].code[k])) return fail(ctx, "code must be finite (object " + std::to_string(i) + ")");
+    std::memcpy(&hz[(size_t)i * CODE], in[i].code, sizeof(float) * dec->code_len);   // a 32-D code: zero-padded
+  }
+  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  sc->n_obj = -1;                    // (an error below leaves no half-uploaded map behind)
+  sc->q_obj = -1;
+  if (n_obj > 0) {
+    DSR_CHECK(ctx, hipMemcpy(sc->objs, ho.data(), sizeof(SceneObj) * n_obj, hipMemcpyHostToDevice));
+    DSR_CHECK(ctx, hipMemcpy(sc->codes, hz.data(), sizeof(float) * CODE * n_obj, hipMemcpyHostToDevice));
+    for (int i = 0; i < n_obj; ++i)
+      hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, dec->D, (const float*)sc->codes + (size_t)i * CODE,
+                         sc->b0 + (size_t)i * HID, sc->b4 + (size_t)i * HID);
+    DSR_CHECK(ctx, hipGetLastError());
+    DSR_CHECK(ctx, hipStreamSynchronize(s));
+  }
+  sc->hobjs = std::move(ho);
+  sc->n_obj = n_obj;
+  return 0;
+}
+
+// objects per pass: SCENE_PASS_OBJ, or DSR_SCENE_PASS_OBJ (1..64) under DSR_TEST_HOOKS=1
+static int scene_pass_obj() {
+  const char* e = hook_env("DSR_SCENE_PASS_OBJ");
+  const int v = e ? atoi(e) : SCENE_PASS_OBJ;
+  return v >= 1 && v <= SCENE_PASS_OBJ ? v : SCENE_PASS_OBJ;
+}
+
+// The value pass of objects obj0 .. obj0 + k - 1 over the resident points, enqueued: bin, scan,
+// emit, the exact decode and (composite) the min and the per-object sums.  The caller has set
+// desc[obj].cand_off = (obj - obj0) * n_pts.  timing: events around the three stages.
+static int scene_value_pass(dsr_scene* sc, int obj0, int k, int n_pts, bool composite, bool timing) {
+  dsr_ctx* ctx = sc->ctx;
+  hipStream_t s = ctx->stream;
+  const DevDecoder& D = sc->dec->D;
+  const int nc = (n_pts + SCHUNK - 1) / SCHUNK, n_chunk = k * nc;
+  const int grid = std::max(1, std::min(ctx->n_cu, k * ((n_pts + TILE - 1) / TILE)));
+  if (timing) DSR_CHECK(ctx, hipEventRecord(sc->ev[0], s));
+  hipLaunchKernelGGL(k_sc_bin, dim3(n_chunk), dim3(SCHUNK), 0, s, obj0, nc, n_pts, (const SceneObj*)sc->objs,
+                     (const float*)sc->pts, sc->ccnt);
+  hipLaunchKernelGGL(k_sc_scan, dim3(1), dim3(RT_SCAN_THREADS), 0, s, n_chunk, nc, obj0, k, (const int*)sc->ccnt,
+                     sc->gpos, sc->ocount, sc->otile, sc->ntiles);
+  hipLaunchKernelGGL(k_sc_emit, dim3(n_chunk), dim3(SCHUNK), 0, s, obj0, nc, n_pts, (const SceneObj*)sc->objs,
+                     (const float*)sc->pts, (const unsigned long long*)sc->keys, (const int*)sc->gpos,
+                     (const int*)sc->ocount, (const int*)sc->otile, sc->cand, sc->tiles, 0);
+  if (timing) DSR_CHECK(ctx, hipEventRecord(sc->ev[1], s));
+  hipLaunchKernelGGL(fwd_kernel_for(D, query_fwd_variant()), dim3(grid), dim3(512), 0, s, D, (const Tile*)sc->tiles,
+                     (const int*)sc->ntiles, (const ObjDesc*)sc->desc, (const float4*)sc->cand, (const float*)sc->b0,
+                     (const float*)sc->b4, sc->dense, (unsigned*)nullptr, ErtArgs{nullptr, 1, 0.f, nullptr, nullptr},
+                     MaskArgs{nullptr, nullptr, nullptr, nullptr});
+  if (timing) DSR_CHECK(ctx, hipEventRecord(sc->ev[2], s));
+  if (composite) {
+    hipLaunchKernelGGL(k_sc_min, dim3(grid), dim3(TILE), 0, s, (const SceneObj*)sc->objs, (const ObjDesc*)sc->desc,
+                       (const Tile*)sc->tiles, (const int*)sc->ntiles, (const float4*)sc->cand, (const float*)sc->dense,
+                       sc->keys, sc->part);
+    hipLaunchKernelGGL(k_sc_sums, dim3(k), dim3(64), 0, s, obj0, (const int*)sc->ocount, (const int*)sc->otile,
+                       (const ScenePart*)sc->part, sc->sums);
+  }
+  if (timing) DSR_CHECK(ctx, hipEventRecord(sc->ev[3], s));
+  DSR_CHECK(ctx, hipGetLastError());
+  sc->held0 = obj0;
+  sc->held_k = k;
+  return 0;
+}
+
+int dsr_scene_query(dsr_scene* sc, int n_pts, const float* pts_world, float* dist, int* obj, float* grad,
+                    dsr_scene_object_out* per_obj) {
+  if (!sc) return -2;
+  dsr_ctx* ctx = sc->ctx;
+  if (n_pts < 0 || n_pts > sc->max_pts) return fail(ctx, "n_pts must be in [0, max_pts]");
+  if (n_pts > 0 && (!pts_world || !dist || !obj)) return fail(ctx, "null argument");
+  if (sc->n_obj < 0) return fail(ctx, "dsr_scene_query before dsr_scene_set_objects");
+  if (!variant_kernels_ok(sc->dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  const int n_obj = sc->n_obj;
+  const DevDecoder& D = sc->dec->D;
+  dsr_scene_stats st{};
+  st.n_obj = n_obj;
+  st.n_pts = n_pts;
+  st.pairs = (long long)n_obj * n_pts;
+  sc->q_obj = -1;
+  sc->held_k = 0;
+  sc->q_in.assign(n_obj, 0);
+  if (per_obj)
+    for (int i = 0; i < n_obj; ++i) per_obj[i] = dsr_scene_object_out{};
+  if (n_obj == 0 || n_pts == 0) {      // nothing to decode: +inf, -1 and zeros
+    for (int p = 0; p < n_pts; ++p) {
+      dist[p] = INFINITY;
+      obj[p] = -1;
+      if (grad) grad[p * 3] = grad[p * 3 + 1] = grad[p * 3 + 2] = 0.f;
+    }
+    sc->st = st;
+    sc->q_obj = n_obj;
+    sc->q_pts = n_pts;
+    return 0;
+  }
+  hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  float* lnw = nullptr;          // LayerNorm decoders: the context stream's Jacobian workspace
+  if (grad && D.ln_mask && !(lnw = ln_workspace(ctx, 0))) return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
+  if (grad && !sc->raw) {
+    const size_t np = (size_t)sc->max_pts + (size_t)TILE * SCENE_PASS_OBJ;
+    if (!scene_alloc(sc, (void**)&sc->grad, sizeof(float) * 3 * sc->max_pts) ||
+        !scene_alloc(sc, (void**)&sc->gcand, sizeof(float4) * np) ||
+        !scene_alloc(sc, (void**)&sc->raw, sizeof(float) * (IN + 1) * np)) {
+      sc->raw = nullptr;
+      return fail(ctx, "hipMalloc failed (scene gradient)");
+    }
+  }
+  // ---- passes: objects in input order, the largest k <= 64 with k * n_pts pairs in the buffers
+  const int k_pass = (int)std::min<size_t>((size_t)scene_pass_obj(), sc->cap / (size_t)n_pts);
+  for (int i = 0; i < n_obj; ++i) {
+    sc->hdesc[i] = ObjDesc{};
+    sc->hdesc[i].cand_off = (i % k_pass) * n_pts;
+  }
+  DSR_CHECK(ctx, hipMemcpy(sc->pts, pts_world, sizeof(float) * 3 * n_pts, hipMemcpyHostToDevice));
+  DSR_CHECK(ctx, hipMemcpy(sc->desc, sc->hdesc.data(), sizeof(ObjDesc) * n_obj, hipMemcpyHostToDevice));
+  DSR_CHECK(ctx, hipMemsetAsync(sc->keys, 0xff, sizeof(unsigned long long) * n_pts, s));
+  DSR_CHECK(ctx, hipMemsetAsync(sc->nwin, 0, sizeof(int) * n_obj, s));
+  for (int o0 = 0; o0 < n_obj; o0 += k_pass) {
+    const int k = std::min(k_pass, n_obj - o0);
+    st.n_passes += 1;
+    if (int rc = scene_value_pass(sc, o0, k, n_pts, true, true)) return rc;
+    DSR_CHECK(ctx, hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1]) == hipSuccess) st.bin_ms += ms;
+    if (hipEventElapsedTime(&ms, sc->ev[1], sc->ev[2]) == hipSuccess) st.decode_ms += ms;
+    if (hipEventElapsedTime(&ms, sc->ev[2], sc->ev[3]) == hipSuccess) st.resolve_ms += ms;
+  }
+  // ---- resolve, n_win, the gradient at the winners
+  const int nc = (n_pts + SCHUNK - 1) / SCHUNK;
+  DSR_CHECK(ctx, hipEventRecord(sc->ev[0], s));
+  hipLaunchKernelGGL(k_sc_resolve, dim3((n_pts + 255) / 256), dim3(256), 0, s, (const unsigned long long*)sc->keys, n_pts,
+                     sc->dist, sc->obj);
+  if (grad) DSR_CHECK(ctx, hipMemsetAsync(sc->grad, 0, sizeof(float) * 3 * n_pts, s));
+  DSR_CHECK(ctx, hipEventRecord(sc->ev[1], s));
+  for (int o0 = 0; o0 < n_obj; o0 += k_pass) {
+    const int k = std::min(k_pass, n_obj - o0);
+    hipLaunchKernelGGL(k_sc_winners, dim3(k * nc), dim3(SCHUNK), 0, s, o0, nc, n_pts, (const unsigned long long*)sc->keys,
+                       sc->ccnt, sc->nwin);
+    if (!grad) continue;
+    const int grid = std::max(1, std::min(ctx->n_cu, (n_pts + TILE - 1) / TILE + k));
+    hipLaunchKernelGGL(k_sc_scan, dim3(1), dim3(RT_SCAN_THREADS), 0, s, k * nc, nc, o0, k, (const int*)sc->ccnt, sc->gpos,
+                       sc->wcount, sc->wtile, sc->ntiles);
+    hipLaunchKernelGGL(k_sc_emit, dim3(k * nc), dim3(SCHUNK), 0, s, o0, nc, n_pts, (const SceneObj*)sc->objs,
+                       (const float*)sc->pts, (const unsigned long long*)sc->keys, (const int*)sc->gpos,
+                       (const int*)sc->wcount, (const int*)sc->wtile, sc->gcand, sc->tiles, 1);
+    hipLaunchKernelGGL(jac_kernel_for(D), dim3(grid), dim3(512), 0, s, D, (const Tile*)sc->tiles, (const int*)sc->ntiles,
+                       (const ObjDesc*)sc->desc, (const ObjState*)nullptr, (const float*)nullptr,
+                       (const float4*)nullptr, (const float*)nullptr, (const float*)sc->b0, (const float*)sc->b4,
+                       GNParams{}, (float*)nullptr, (const float4*)sc->gcand, sc->raw, (float*)nullptr,
+                       MaskArgs{nullptr, nullptr, nullptr, nullptr}, lnw);
+    hipLaunchKernelGGL(k_sc_grad, dim3(grid), dim3(TILE), 0, s, (const SceneObj*)sc->objs, (const Tile*)sc->tiles,
+                       (const int*)sc->ntiles, (const float4*)sc->gcand, (const float*)sc->raw, sc->grad);
+  }
+  DSR_CHECK(ctx, hipEventRecord(sc->ev[2], s));
+  DSR_CHECK(ctx, hipGetLastError());
+  DSR_CHECK(ctx, hipStreamSynchronize(s));
+  // (blocking copies after the synchronise: an error return never leaves a copy in flight)
+  DSR_CHECK(ctx, hipMemcpy(dist, sc->dist, sizeof(float) * n_pts, hipMemcpyDeviceToHost));
+  DSR_CHECK(ctx, hipMemcpy(obj, sc->obj, sizeof(int) * n_pts, hipMemcpyDeviceToHost));
+  if (grad) DSR_CHECK(ctx, hipMemcpy(grad, sc->grad, sizeof(float) * 3 * n_pts, hipMemcpyDeviceToHost));
+  std::vector<int> hwin(n_obj);
+  std::vector<SceneSums> hs(n_obj);
+  DSR_CHECK(ctx, hipMemcpy(sc->q_in.data(), sc->ocount, sizeof(int) * n_obj, hipMemcpyDeviceToHost));
+  DSR_CHECK(ctx, hipMemcpy(hwin.data(), sc->nwin, sizeof(int) * n_obj, hipMemcpyDeviceToHost));
+  DSR_CHECK(ctx, hipMemcpy(hs.data(), sc->sums, sizeof(SceneSums) * n_obj, hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1]) == hipSuccess) st.resolve_ms += ms;
+  if (hipEventElapsedTime(&ms, sc->ev[1], sc->ev[2]) == hipSuccess) (grad ? st.grad_ms : st.resolve_ms) += ms;
+  for (int i = 0; i < n_obj; ++i) {
+    st.decoded += sc->q_in[i];
+    st.winners += hwin[i];
+    if (per_obj) per_obj[i] = dsr_scene_object_out{sc->q_in[i], hwin[i], hs[i].n_neg, hs[i].n_nan, hs[i].sum, hs[i].sum_abs};
+  }
+  sc->st = st;
+  sc->q_obj = n_obj;
+  sc->q_pts = n_pts;
+  return 0;
+}
+
+int dsr_scene_peek(dsr_scene* sc, int obj, int cap, int* idx, float* x_obj, float* sdf, int* n) {
+  if (!sc) return -2;
+  dsr_ctx* ctx = sc->ctx;
+  if (!n || cap < 0) return fail(ctx, "null argument");
+  if (sc->q_obj < 0 || obj < 0 || obj >= sc->q_obj) return fail(ctx, "dsr_scene_peek: object outside the last query");
+  const int cnt = sc->q_in[obj], n_pts = sc->q_pts;
+  *n = cnt;
+  if (cnt > cap) return -5;
+  if (cnt == 0) return 0;
+  hipSetDevice(ctx->device);
+  if (obj < sc->held0 || obj >= sc->held0 + sc->held_k) {
+    // an earlier pass's object: its value pass again, alone (the same tiles, so the same values)
+    sc->hdesc[obj].cand_off = 0;
+    DSR_CHECK(ctx, hipMemcpy(sc->desc + obj, &sc->hdesc[obj], sizeof(ObjDesc), hipMemcpyHostToDevice));
+    if (int rc = scene_value_pass(sc, obj, 1, n_pts, false, false)) return rc;
+    DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  const size_t off = (size_t)(obj - sc->held0) * n_pts;
+  std::vector<float4> hc(cnt);
+  std::vector<float> hd(n_pts);
+  DSR_CHECK(ctx, hipMemcpy(hc.data(), sc->cand + off, sizeof(float4) * cnt, hipMemcpyDeviceToHost));
+  DSR_CHECK(ctx, hipMemcpy(hd.data(), sc->dense + off, sizeof(float) * n_pts, hipMemcpyDeviceToHost));
+  for (int j = 0; j < cnt; ++j) {
+    int i;
+    std::memcpy(&i, &hc[j].w, sizeof(int));
+    if (idx) idx[j] = i;
+    if (x_obj) {
+      x_obj[j * 3] = hc[j].x;
+      x_obj[j * 3 + 1] = hc[j].y;
+      x_obj[j * 3 + 2] = hc[j].z;
+    }
+    if (sdf) sdf[j] = hd[i];
+  }
   return 0;
 }
 

@@ -15,7 +15,8 @@
  *                              pose-only single and batched (including an empty object), the
  *                              mesher (and dsr_mc_volume on its decoded grid) with ample and
  *                              with too small capacities, the batch call (dsr_mesher_run_batch:
- *                              ample and too small totals, n = 0) against it, forced audit
+ *                              ample and too small totals, n = 0) against it, scene queries
+ *                              (dsr_scene_*) against sdf_eval and their records, forced audit
  *                              violations and their spare-iteration redo (test hooks), and the
  *                              error paths of a live context.  Exit status 0 = every check held.
  */
@@ -183,6 +184,50 @@ static void no_device_paths(void) {
     ro[0].t_cam_obj[15] = 1.f;
     ro[0].t_cam_obj[0] = -1.f;
     CHECK(dsr_render_layout(&cam, 0.01f, 1, ro, rect, status) < 0, "render_layout(reflection) accepted");
+  }
+  {
+    /* the scene query: null arguments, and the host-only binning rule (dsr_scene_bin_host) — a
+       scale-2 object at the origin and a unit one at x = 3, seven points, then a capacity too
+       small, a bad object index, a bad last row, a reflected and a non-finite pose */
+    dsr_scene* sc = NULL;
+    CHECK(dsr_scene_create(NULL, NULL, 4, 64, &sc) < 0 && sc == NULL, "scene_create(NULL ctx) accepted");
+    CHECK(dsr_scene_create(NULL, NULL, 4, 64, NULL) < 0, "scene_create(NULL) accepted");
+    CHECK(dsr_scene_destroy(NULL) == 0, "scene_destroy(NULL)");
+    CHECK(dsr_scene_set_objects(NULL, 0, NULL) < 0, "scene_set_objects(NULL) accepted");
+    CHECK(dsr_scene_query(NULL, 0, NULL, NULL, NULL, NULL, NULL) < 0, "scene_query(NULL) accepted");
+    CHECK(dsr_scene_peek(NULL, 0, 0, NULL, NULL, NULL, NULL) < 0, "scene_peek(NULL) accepted");
+    CHECK(dsr_scene_stats_get(NULL, NULL) < 0, "scene_stats_get(NULL) accepted");
+    dsr_scene_object so[2];
+    memset(so, 0, sizeof(so));
+    for (int i = 0; i < 3; ++i) so[0].t_world_obj[i * 5] = 2.f;
+    for (int i = 0; i < 3; ++i) so[1].t_world_obj[i * 5] = 1.f;
+    so[0].t_world_obj[15] = so[1].t_world_obj[15] = 1.f;
+    so[1].t_world_obj[3] = 3.f;
+    const float inf = INFINITY;
+    const float pw[7 * 3] = {0.f, 0.f, 0.f,   1.5f, 0.f, 0.f,   2.5f, 0.f, 0.f,   3.5f, 0.5f, 0.f,
+                             0.f, -1.9f, 0.f, inf, 0.f, 0.f,    0.f, NAN, 0.f};
+    int idx[7], n_in = -1;
+    float xo[7 * 3], scale = 0.f;
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) == 0, "scene_bin_host failed");
+    CHECK(n_in == 3 && idx[0] == 0 && idx[1] == 1 && idx[2] == 4 && scale == 2.f, "scene_bin_host object 0: %d", n_in);
+    CHECK(xo[3] == 0.75f && xo[4] == 0.f && xo[7] == -0.95f, "scene_bin_host coordinates %g %g", xo[3], xo[7]);
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 1, 7, idx, xo, &n_in, &scale) == 0, "scene_bin_host failed (1)");
+    CHECK(n_in == 2 && idx[0] == 2 && idx[1] == 3 && scale == 1.f && xo[0] == -0.5f, "scene_bin_host object 1: %d", n_in);
+    idx[0] = -9;
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 2, idx, xo, &n_in, NULL) == -5 && n_in == 3 && idx[0] == -9,
+          "scene_bin_host(cap 2): count without copying");
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 0, NULL, NULL, &n_in, NULL) == -5 && n_in == 3, "scene_bin_host(count only)");
+    CHECK(dsr_scene_bin_host(2, so, 0, NULL, 0, 0, NULL, NULL, &n_in, NULL) == 0 && n_in == 0, "scene_bin_host(n_pts 0)");
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 2, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(obj 2) accepted");
+    CHECK(dsr_scene_bin_host(0, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(n_obj 0) accepted");
+    CHECK(dsr_scene_bin_host(2, so, 7, NULL, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(NULL points) accepted");
+    so[1].t_world_obj[15] = 2.f;
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(last row) accepted");
+    so[1].t_world_obj[15] = 1.f;
+    so[1].t_world_obj[0] = -1.f;
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(reflection) accepted");
+    so[1].t_world_obj[0] = inf;
+    CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(inf pose) accepted");
   }
   dsr_ctx* c = NULL;
   const int rc2 = dsr_ctx_create(-7, &c);
@@ -555,6 +600,79 @@ int main(int argc, char** argv) {
     CHECK(memcmp(T1, Tb, sizeof T1) == 0 && memcmp(T1, Tb + 32, sizeof T1) == 0, "pose batch != single");
     CHECK(isnan(Tb[16]), "empty object not NaN");
     free(x); free(s0); free(s1); free(J);
+  }
+
+  /* scene queries: an identity-pose object is dsr_sdf_eval bitwise; a second, scale-2 object
+     shifted by 1.5 shares the call; too many points / objects, a query before set_objects, a peek
+     with too small a capacity and one outside the query are refused */
+  if (run_section("scene")) {
+    const int n = 500;
+    float* x = (float*)malloc(sizeof(float) * 3 * n);
+    float* s0 = (float*)malloc(sizeof(float) * n);
+    float* dist = (float*)malloc(sizeof(float) * n);
+    float* g = (float*)malloc(sizeof(float) * 3 * n);
+    float* pf = (float*)malloc(sizeof(float) * n);
+    float* px = (float*)malloc(sizeof(float) * 3 * n);
+    int* who = (int*)malloc(sizeof(int) * n);
+    int* pidx = (int*)malloc(sizeof(int) * n);
+    unsigned r = 777u;
+    for (int i = 0; i < n; ++i) {                     /* in the ball of radius 0.9 */
+      float q[3], nn;
+      do {
+        for (int k = 0; k < 3; ++k) {
+          r = r * 1664525u + 1013904223u;
+          q[k] = ((float)(r >> 8) / 16777216.f) * 1.8f - 0.9f;
+        }
+        nn = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+      } while (nn >= 0.81f);
+      memcpy(x + 3 * i, q, sizeof q);
+    }
+    dsr_scene* sc = NULL;
+    CHECK(dsr_scene_create(ctx, dec, 0, n, &sc) < 0 && sc == NULL, "scene max_obj 0 accepted");
+    CHECK(dsr_scene_create(ctx, dec, 2, n, &sc) == 0 && sc != NULL, "%s", dsr_last_error(ctx));
+    CHECK(dsr_scene_query(sc, n, x, dist, who, NULL, NULL) < 0, "query before set_objects accepted");
+    dsr_scene_object so[3];
+    memset(so, 0, sizeof(so));
+    for (int k = 0; k < 3; ++k) {
+      for (int i = 0; i < 4; ++i) so[k].t_world_obj[i * 5] = 1.f;
+      so[k].code = ref[0].code;
+    }
+    for (int i = 0; i < 3; ++i) so[1].t_world_obj[i * 5] = 2.f;
+    so[1].t_world_obj[3] = 1.5f;
+    CHECK(dsr_scene_set_objects(sc, 3, so) < 0, "n_obj > max_obj accepted");
+    CHECK(dsr_scene_set_objects(sc, 1, so) == 0, "%s", dsr_last_error(ctx));
+    CHECK(dsr_scene_query(sc, n + 1, x, dist, who, NULL, NULL) < 0, "n_pts > max_pts accepted");
+    dsr_scene_object_out rec[2];
+    CHECK(dsr_scene_query(sc, n, x, dist, who, NULL, rec) == 0, "%s", dsr_last_error(ctx));
+    CHECK(dsr_sdf_eval(ctx, dec, ref[0].code, x, n, s0, NULL) == 0, "%s", dsr_last_error(ctx));
+    CHECK(memcmp(dist, s0, sizeof(float) * n) == 0, "identity-pose scene query != sdf_eval");
+    CHECK(rec[0].n_in == n && rec[0].n_win == n && rec[0].n_nan == 0, "scene record %d %d", rec[0].n_in, rec[0].n_win);
+    for (int i = 0; i < n; ++i) CHECK(who[i] == 0, "obj %d", i);
+    CHECK(dsr_scene_set_objects(sc, 2, so) == 0, "%s", dsr_last_error(ctx));
+    CHECK(dsr_scene_query(sc, n, x, dist, who, g, rec) == 0, "%s", dsr_last_error(ctx));
+    CHECK(rec[0].n_in == n && rec[1].n_in > 0 && rec[1].n_in < n && rec[0].n_win + rec[1].n_win == n, "two-object records");
+    for (int i = 0; i < n; ++i) {
+      CHECK(who[i] == 0 || who[i] == 1, "obj %d", i);
+      CHECK(who[i] == 1 ? dist[i] < s0[i] : dist[i] == s0[i], "dist %d", i);
+      CHECK(isfinite(g[3 * i]) && isfinite(g[3 * i + 1]) && isfinite(g[3 * i + 2]), "grad %d", i);
+    }
+    int cnt = -1;
+    CHECK(dsr_scene_peek(sc, 1, 0, NULL, NULL, NULL, &cnt) == -5 && cnt == rec[1].n_in, "peek count %d", cnt);
+    CHECK(dsr_scene_peek(sc, 1, n, pidx, px, pf, &cnt) == 0 && cnt == rec[1].n_in, "%s", dsr_last_error(ctx));
+    double sum = 0.0;
+    for (int j = 0; j < cnt; ++j) {
+      CHECK(pidx[j] >= 0 && pidx[j] < n && (j == 0 || pidx[j] > pidx[j - 1]), "peek order %d", j);
+      CHECK(px[3 * j] == 0.5f * x[3 * pidx[j]] - 0.75f, "peek x %d", j);
+      sum += pf[j];
+    }
+    CHECK(fabs(sum - rec[1].sum_sdf) <= 1e-9 * cnt, "sum_sdf %g %g", sum, rec[1].sum_sdf);
+    CHECK(dsr_scene_peek(sc, 2, n, pidx, px, pf, &cnt) < 0, "peek outside the query accepted");
+    dsr_scene_stats sst;
+    CHECK(dsr_scene_stats_get(sc, &sst) == 0 && sst.n_obj == 2 && sst.n_pts == n && sst.n_passes == 1 &&
+          sst.pairs == 2 * n && sst.decoded == rec[0].n_in + rec[1].n_in && sst.winners == n, "scene stats");
+    CHECK(dsr_scene_query(sc, 0, NULL, NULL, NULL, NULL, rec) == 0 && rec[0].n_in == 0, "n_pts 0: %s", dsr_last_error(ctx));
+    CHECK(dsr_scene_destroy(sc) == 0, "scene_destroy");
+    free(x); free(s0); free(dist); free(g); free(pf); free(px); free(who); free(pidx);
   }
 
   /* mesher: a d^3 grid over [-1, 1]^3, ample capacities, then too small ones (-5, counts) */

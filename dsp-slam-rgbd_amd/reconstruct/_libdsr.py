@@ -152,6 +152,24 @@ class RenderStats(C.Structure):
 RENDER_OK, RENDER_OFFSCREEN, RENDER_SKIP_NEAR = 0, 1, 2   # include/dsr.h DSR_RENDER_*
 
 
+class SceneObject(C.Structure):
+    """dsr_scene_object: the object->world Sim(3) (row-major) and the code of one map object."""
+    _fields_ = [("t_world_obj", C.c_float * 16), ("code", FP)]
+
+
+class SceneObjectOut(C.Structure):
+    """dsr_scene_object_out: one object's record of a dsr_scene_query call (include/dsr.h)."""
+    _fields_ = [("n_in", C.c_int), ("n_win", C.c_int), ("n_neg", C.c_int), ("n_nan", C.c_int),
+                ("sum_sdf", C.c_double), ("sum_abs", C.c_double)]
+
+
+class SceneStats(C.Structure):
+    """dsr_scene_stats: the last dsr_scene_query call of a scene (include/dsr.h)."""
+    _fields_ = [("n_obj", C.c_int), ("n_pts", C.c_int), ("n_passes", C.c_int), ("pairs", C.c_longlong),
+                ("decoded", C.c_longlong), ("winners", C.c_longlong), ("bin_ms", C.c_double),
+                ("decode_ms", C.c_double), ("resolve_ms", C.c_double), ("grad_ms", C.c_double)]
+
+
 class FrameParams(C.Structure):
     """dsr_frame_params: every value is taken literally (dsr_frame_params_default fills the defaults)."""
     _fields_ = [("max_pts", C.c_int), ("max_bg", C.c_int), ("downsample", C.c_int), ("expand", C.c_int),
@@ -239,6 +257,14 @@ SIGNATURES = {
     "dsr_renderer_stats_get": (C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
     "dsr_renderer_destroy": (C.c_int, [C.c_void_p]),
     "dsr_render_layout": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_int, C.POINTER(RenderObject), IP, IP]),
+    "dsr_scene_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "dsr_scene_set_objects": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SceneObject)]),
+    "dsr_scene_query": (C.c_int, [C.c_void_p, C.c_int, FP, FP, IP, FP, C.POINTER(SceneObjectOut)]),
+    "dsr_scene_peek": (C.c_int, [C.c_void_p, C.c_int, C.c_int, IP, FP, FP, IP]),
+    "dsr_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(SceneStats)]),
+    "dsr_scene_destroy": (C.c_int, [C.c_void_p]),
+    "dsr_scene_bin_host": (C.c_int, [C.c_int, C.POINTER(SceneObject), C.c_int, FP, C.c_int, C.c_int, IP, FP, IP,
+                                     FP]),
     "dsr_frame_params_default": (C.c_int, [C.POINTER(FrameParams)]),
     "dsr_frame_inputs_host": (C.c_int, [C.POINTER(Camera), C.POINTER(FrameParams), FP, IP, C.c_int,
                                         C.POINTER(FrameDet), FP, FP, FP, C.POINTER(FrameDetOut)]),
@@ -253,7 +279,9 @@ SIGNATURES = {
 #: library of the same ABI number built before them still loads (A/B runs under DSR_LIB)
 BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_render", "dsr_renderer_stats_get",
              "dsr_renderer_destroy", "dsr_render_layout", "dsr_frame_params_default", "dsr_frame_inputs_host",
-             "dsr_frame_inputs", "dsr_batch_refill_frame", "dsr_batch_frame_info")
+             "dsr_frame_inputs", "dsr_batch_refill_frame", "dsr_batch_frame_info", "dsr_scene_create",
+             "dsr_scene_set_objects", "dsr_scene_query", "dsr_scene_peek", "dsr_scene_stats_get", "dsr_scene_destroy",
+             "dsr_scene_bin_host")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

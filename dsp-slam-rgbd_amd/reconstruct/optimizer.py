@@ -820,3 +820,131 @@ class SdfRenderer(object):
         if rc != 0:
             raise L.DsrError(f"dsr_renderer_stats_get failed ({rc})")
         return {k: getattr(st, k) for k, _ in L.RenderStats._fields_}
+
+
+def _scene_objects(objects, code_len):
+    """[(t_world_obj (4,4), code or None), ...] -> (SceneObject array, the arrays it points into)"""
+    ins = (L.SceneObject * max(len(objects), 1))()
+    keep = []
+    for i, (t, code) in enumerate(objects):
+        t = np.ascontiguousarray(np.asarray(t, np.float32).reshape(16))
+        ins[i].t_world_obj[:] = t.tolist()
+        if code is not None:
+            c = _code(code, code_len)
+            keep.append(c)
+            ins[i].code = L.fptr(c)
+    return ins, keep
+
+
+def scene_bin(objects, pts_world, i):
+    """The binning rule of ``SceneSdf.query`` on the host (dsr_scene_bin_host; no device): the
+    indices of the points inside object ``i``'s unit ball, in point order, their object-frame
+    coordinates and the object's scale s — the inside test of MapObject::compute_sdf_loss
+    (src/MapObject_util.cc:9-69) made exact.  ``objects``: ``[(t_world_obj (4,4), code), ...]``
+    (the codes are not read)."""
+    lib = L.load_library()
+    if not hasattr(lib, "dsr_scene_bin_host"):
+        raise L.DsrError("this libdsr was built without dsr_scene_* (no fallback)")
+    pts = _f32(pts_world, 3)
+    ins, _ = _scene_objects([(t, None) for t, _ in objects], 0)
+    n = pts.shape[0]
+    idx = np.zeros(n, np.int32)
+    x = np.zeros((n, 3), np.float32)
+    cnt, s = C.c_int(), C.c_float()
+    rc = lib.dsr_scene_bin_host(len(objects), ins, n, L.fptr(pts), int(i), n, L.iptr(idx), L.fptr(x),
+                                C.cast(C.byref(cnt), L.IP), C.cast(C.byref(s), L.FP))
+    if rc != 0:
+        raise L.DsrError(f"dsr_scene_bin_host failed ({rc}): bad argument or pose")
+    return idx[:cnt.value].copy(), x[:cnt.value].copy(), float(s.value)
+
+
+class SceneSdf(object):
+    """World points against every object of a map at once, on device (dsr_scene_*; DESIGN.md
+    §3.6c).  Replaces the per-object loop of MapObject::compute_sdf_loss /
+    compute_sdf_loss_of_all_inside_points (src/MapObject_util.cc:9-69) over
+    ``Optimizer.compute_sdf_loss_objectpoint_zhjd`` (reconstruct/optimizer.py:207-213) and the
+    per-vertex collision check of the planner (src/NbvGenerator.cpp:320-327): the objects' poses
+    and folded codes stay resident, a query uploads the points once."""
+
+    def __init__(self, decoder, max_obj, max_pts, code_len=64):
+        self.decoder = decoder
+        self.code_len = code_len
+        self.max_obj, self.max_pts = int(max_obj), int(max_pts)
+        self._n_obj = 0
+        ctx = decoder.ctx
+        if not hasattr(ctx.lib, "dsr_scene_create"):
+            raise L.DsrError("this libdsr was built without dsr_scene_* (no fallback)")
+        h = C.c_void_p()
+        ctx.check(ctx.lib.dsr_scene_create(ctx.handle, decoder.handle, self.max_obj, self.max_pts, C.byref(h)),
+                  "dsr_scene_create")
+        self._h = h
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self.decoder.ctx.lib.dsr_scene_destroy(h)
+            except Exception:
+                pass
+        self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _handle(self):
+        if self._h is None:
+            raise L.DsrError("scene is closed")
+        return self._h
+
+    def set_objects(self, objects):
+        """``objects``: a list of ``(t_world_obj (4,4), code)`` — MapObject::Sim3Two and vShapeCode.
+        The codes are folded on device here, once."""
+        ctx = self.decoder.ctx
+        ins, keep = _scene_objects(objects, self.code_len)
+        ctx.check(ctx.lib.dsr_scene_set_objects(self._handle(), len(objects), ins), "dsr_scene_set_objects")
+        self._n_obj = len(objects)
+
+    def query(self, pts_world, grad=False):
+        """``pts_world`` (n,3).  Returns dist (n,) f32 (the smallest s_i f_i over the balls that hold
+        the point, +inf in no ball), obj (n,) i32 (its object, -1 in no ball; ties go to the lower
+        index), grad (n,3) f32 (the world-frame gradient of dist, 0 where nothing won) or None, and
+        ``objects``: per object n_in, n_win, n_neg, n_nan, sum_sdf, sum_abs and mean_sdf = sum_sdf /
+        n_in — compute_sdf_loss_objectpoint_zhjd on the points inside its ball (NaN when empty)."""
+        ctx = self.decoder.ctx
+        pts = _f32(pts_world, 3)
+        n = pts.shape[0]
+        dist = np.zeros(n, np.float32)
+        obj = np.zeros(n, np.int32)
+        g = np.zeros((n, 3), np.float32) if grad else None
+        outs = (L.SceneObjectOut * max(self._n_obj, 1))()
+        ctx.check(ctx.lib.dsr_scene_query(self._handle(), n, L.fptr(pts), L.fptr(dist), L.iptr(obj), L.fptr(g), outs),
+                  "dsr_scene_query")
+        recs = [ForceKeyErrorDict(n_in=o.n_in, n_win=o.n_win, n_neg=o.n_neg, n_nan=o.n_nan, sum_sdf=o.sum_sdf,
+                                  sum_abs=o.sum_abs, mean_sdf=o.sum_sdf / o.n_in if o.n_in else float("nan"))
+                for o in outs[:self._n_obj]]
+        return ForceKeyErrorDict(dist=dist, obj=obj, grad=g, objects=recs)
+
+    def peek(self, i):
+        """Diagnostic (dsr_scene_peek): object ``i``'s candidates of the last query in point order —
+        their point indices, object-frame coordinates and decoded f."""
+        ctx = self.decoder.ctx
+        n = C.c_int()
+        rc = ctx.lib.dsr_scene_peek(self._handle(), int(i), 0, None, None, None, C.cast(C.byref(n), L.IP))
+        if rc not in (0, -5):
+            ctx.check(rc, "dsr_scene_peek")
+        cnt = n.value
+        idx = np.zeros(cnt, np.int32)
+        x = np.zeros((cnt, 3), np.float32)
+        sdf = np.zeros(cnt, np.float32)
+        if cnt:
+            ctx.check(ctx.lib.dsr_scene_peek(self._handle(), int(i), cnt, L.iptr(idx), L.fptr(x), L.fptr(sdf),
+                                             C.cast(C.byref(n), L.IP)), "dsr_scene_peek")
+        return idx, x, sdf
+
+    def stats(self):
+        """dsr_scene_stats of the last ``query`` call, as a dict."""
+        st = L.SceneStats()
+        rc = self.decoder.ctx.lib.dsr_scene_stats_get(self._handle(), C.byref(st))
+        if rc != 0:
+            raise L.DsrError(f"dsr_scene_stats_get failed ({rc})")
+        return {k: getattr(st, k) for k, _ in L.SceneStats._fields_}

@@ -473,6 +473,76 @@ int dsr_renderer_destroy(dsr_renderer* r);
 int dsr_render_layout(const dsr_camera* cam, float near, int n_obj, const dsr_render_object* objs,
                       int* rect, int* status);
 
+/* ---- scene SDF queries: world points against every map object at once.  Replaces the per-object
+ * loop of MapObject::compute_sdf_loss / compute_sdf_loss_of_all_inside_points
+ * (src/MapObject_util.cc:9-69) over Optimizer.compute_sdf_loss_objectpoint_zhjd
+ * (reconstruct/optimizer.py:207-213), and the per-vertex, per-object collision check of the RRT
+ * planner (src/NbvGenerator.cpp:320-327, commented out in the reference) with one resident query
+ * (DESIGN.md 3.6c states the algorithm exactly).  Callers detect these entry points by symbol; the
+ * ABI number is unchanged.
+ *
+ * Object i: T_ow = inverse(t_world_obj) in fp64 (adjugate / determinant) rounded once to fp32 as
+ * A (3x3) and t, s = det(R)^(1/3) rounded once.  Pair (p, i): x_k = fmaf(A_k0, p_x, fmaf(A_k1, p_y,
+ * fmaf(A_k2, p_z, t_k))), r2 = fmaf(x_0, x_0, fmaf(x_1, x_1, x_2 * x_2)); the pair is a candidate
+ * iff r2 < 1.0f (the in-ball rule of reconstruct/loss.py:82 on the squared norm); a point with a
+ * non-finite coordinate is in no ball.  Object i's candidates, in point order, are decoded exactly
+ * (k_mlp_fwd16) in 64-point tiles from the first, f; d = s * f. */
+typedef struct {
+  float t_world_obj[16];          /* object->world Sim(3), row-major (MapObject::Sim3Two, src/MapObject_util.cc:9-69) */
+  const float* code;              /* (code_len,) (MapObject::vShapeCode, src/MapObject_util.cc:9-69) */
+} dsr_scene_object;
+typedef struct {
+  int n_in;                       /* points inside this object's unit ball (candidates) */
+  int n_win;                      /* points whose nearest object this is */
+  int n_neg;                      /* candidates with f < 0 (inside the surface) */
+  int n_nan;                      /* candidates whose decoded value is NaN (never win, not summed) */
+  double sum_sdf;                 /* sum of f over the candidates: sum_sdf / n_in is
+                                     compute_sdf_loss_objectpoint_zhjd (reconstruct/optimizer.py:207-213) on them */
+  double sum_abs;                 /* sum of |f| */
+} dsr_scene_object_out;
+typedef struct {
+  int n_obj, n_pts, n_passes;
+  long long pairs;                /* n_obj x n_pts */
+  long long decoded;              /* candidates (decoder evaluations of the value pass) */
+  long long winners;              /* points in at least one ball */
+  double bin_ms, decode_ms, resolve_ms, grad_ms;   /* device events, summed over the passes */
+} dsr_scene_stats;
+
+typedef struct dsr_scene dsr_scene;
+/* The resident buffers of a map of at most max_obj objects queried with at most max_pts points
+ * (the object list of src/MapObject_util.cc:9-69's callers).  Errors, before the device is
+ * touched: null arguments, max_obj < 1, max_pts < 1 or > 2^24. */
+int dsr_scene_create(dsr_ctx* ctx, const dsr_decoder* dec, int max_obj, int max_pts, dsr_scene** out);
+/* The map's objects (MapObject::Sim3Two and vShapeCode, src/MapObject_util.cc:9-69): uploads the
+ * inverse poses and folds every code on the device once; queries do not repeat it.  Errors,
+ * returned before the device is touched: null arguments, n_obj outside 0..max_obj, a last row that
+ * is not 0 0 0 1, a determinant <= 0, a non-finite pose entry or code. */
+int dsr_scene_set_objects(dsr_scene* sc, int n_obj, const dsr_scene_object* objs);
+/* compute_sdf_loss_objectpoint_zhjd (reconstruct/optimizer.py:207-213) of every object at n_pts
+ * world points (n x 3), and the nearest object of every point — the collision check of
+ * src/NbvGenerator.cpp:320-327: dist[p] = min_i s_i f_i(x) over the balls that hold p, obj[p] its
+ * object (ties go to the lower index; +inf and -1 in no ball), grad (NULL or n x 3) the world-frame
+ * gradient R g of dist (0 where nothing won), per_obj (NULL or n_obj records).  Bitwise
+ * reproducible and independent of which other objects share the call.  Errors: null arguments,
+ * n_pts outside 0..max_pts, a query before dsr_scene_set_objects. */
+int dsr_scene_query(dsr_scene* sc, int n_pts, const float* pts_world, float* dist, int* obj, float* grad,
+                    dsr_scene_object_out* per_obj);
+/* Diagnostic: object `obj`'s candidates of the last query, in point order — their point indices,
+ * object-frame coordinates and decoded f (the inside points of src/MapObject_util.cc:9-69).  Any
+ * output may be NULL.  *n is the count; cap too small returns it with status -5 and copies nothing
+ * (dsr_mesher_run's convention).  Error: an object outside the last query. */
+int dsr_scene_peek(dsr_scene* sc, int obj, int cap, int* idx, float* x_obj, float* sdf, int* n);
+/* the last dsr_scene_query call (no counterpart in src/MapObject_util.cc:9-69) */
+int dsr_scene_stats_get(const dsr_scene* sc, dsr_scene_stats* st);
+int dsr_scene_destroy(dsr_scene* sc);
+/* Host only, no context, no device: the binning rule above for object `obj` of objs — its
+ * candidates' point indices (idx, cap) and coordinates (x_obj, cap x 3) in point order, their
+ * count *n_in and *scale = s (the inside test of src/MapObject_util.cc:9-69 made exact).  Any
+ * output may be NULL; cap too small returns the count with status -5.  Returns -2 for a bad
+ * argument or pose (no message: there is no context). */
+int dsr_scene_bin_host(int n_obj, const dsr_scene_object* objs, int n_pts, const float* pts_world, int obj,
+                       int cap, int* idx, float* x_obj, int* n_in, float* scale);
+
 /* ---- frame ingest: one depth image + one instance-label image + a list of detections -> every
  * detection's surface points, rays and observed depths (the dsr_object_in arrays), on the host or
  * straight into the slots of a capacity batch on the device.  Replaces the per-detection numpy of
