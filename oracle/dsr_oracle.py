@@ -92,13 +92,21 @@ class Decoder:
             keep[i] = (xh, rstd)
         return xh * g + b
 
-    def forward(self, inp, keep_masks=False, keep_pre=False, keep_ln=None):
-        """inp (n, L+3) -> sdf (n,).  deep_sdf_decoder.py:75-110."""
+    def forward(self, inp, keep_masks=False, keep_pre=False, keep_ln=None, keep_relu_in=None, force=None):
+        """inp (n, L+3) -> sdf (n,).  deep_sdf_decoder.py:75-110.
+
+        Checker hooks (tests/decoder_check.py), inert when absent: ``keep_relu_in`` (a list)
+        receives, per hidden layer, the (n, width) values its ReLU sees (after the LayerNorm
+        where there is one); ``force`` is an integer array of (point, layer, unit, on) rows —
+        that unit's ReLU passes its input at that point if ``on`` and gives 0 otherwise,
+        whatever the input's sign, and the returned masks carry the forced decision."""
         inp = np.asarray(inp, self.dtype)
         xyz = inp[..., -3:]
         x = inp
         masks = []
         n_layers = len(self.layers)
+        if force is not None:
+            force = np.asarray(force, np.int64).reshape(-1, 4)
         for i, (W, b) in enumerate(self.layers):
             if i in self.latent_in:
                 x = np.concatenate([x, inp], axis=-1)          # :87-88
@@ -110,7 +118,12 @@ class Decoder:
             if i < n_layers - 1:
                 if self.norms[i] is not None:
                     x = self._ln(x, i, keep_ln)                # :96-101
+                if keep_relu_in is not None:
+                    keep_relu_in.append(x)
                 m = x > 0
+                if force is not None:
+                    f = force[force[:, 1] == i]
+                    m[f[:, 0], f[:, 2]] = f[:, 3] != 0
                 x = np.where(m, x, self.dtype(0))              # :103 ReLU
                 if keep_masks:
                     masks.append(m)
@@ -120,14 +133,16 @@ class Decoder:
             return y, masks, t
         return (y, masks) if keep_masks else y
 
-    def forward_jac(self, inp):
+    def forward_jac(self, inp, force=None, keep_relu_in=None):
         """(y, dy/dinp) — what ``get_batch_sdf_jacobian`` (loss_utils.py:82-113) gets
         from autograd, restated as the analytic chain rule:
         tanh' = 1-y^2 (use_tanh: times 1-t^2 of the inner tanh), ReLU' = [out>0],
-        Linear' = W^T, latent-skip split at layer 4, xyz_in_all columns to d/dxyz."""
+        Linear' = W^T, latent-skip split at layer 4, xyz_in_all columns to d/dxyz.
+        ``force`` / ``keep_relu_in``: see ``forward``; forward and backward use the forced mask."""
         inp = np.asarray(inp, self.dtype)
         lnk = {}
-        y, masks, t = self.forward(inp, keep_masks=True, keep_pre=True, keep_ln=lnk)
+        y, masks, t = self.forward(inp, keep_masks=True, keep_pre=True, keep_ln=lnk,
+                                   keep_relu_in=keep_relu_in, force=force)
         n_layers = len(self.layers)
         L3 = inp.shape[-1]
         g = (self.dtype(1) - y * y)[:, None]                   # d tanh

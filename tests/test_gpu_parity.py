@@ -85,6 +85,12 @@ def test_decoder_vs_oracle_random(gpu_decoder, oracle_dec):
     y64, j64 = type(oracle_dec)(oracle_dec.layers, dtype=np.float64).forward_jac(inp.astype(np.float64))
     assert np.abs(y - y64).max() <= 2e-5
     assert_jac_close(j, j64, tol=1e-4)
+    # and point by point, kinks attributed (tests/decoder_check.py)
+    import decoder_check as DC
+
+    T = DC.Truth(oracle_dec, type(oracle_dec)(oracle_dec.layers, dtype=np.float64), inp)
+    T.assert_caps()
+    T.check(y, j, DC.R["split"], "bench decoder, 3000 random points")
 
 
 @pytest.mark.parametrize("name,optim,dtype", [("redwood0", S.REDWOOD_OPTIM, "Redwood"),
