@@ -339,6 +339,9 @@ struct dsr_batch {
   void* frame_dev = nullptr;
   size_t frame_host_bytes = 0, frame_dev_bytes = 0;
   int frame_n = -1, frame_w = 0, frame_h = 0;
+  // the last fill was dsr_batch_refill_frame_poses with this max_pts (§3.5c; its keep flags and pose
+  // records follow the ingest's part of frame_dev), else -1
+  int frame_pose_pts = -1;
 };
 
 #define DSR_CHECK(ctx, call)                                                        \
@@ -1553,6 +1556,7 @@ int dsr_batch_refill(dsr_batch* b, int n_obj, const dsr_object_in* in) {
   DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
   b->n_active = n_obj;
   b->frame_n = -1;
+  b->frame_pose_pts = -1;
   b->ran = false;
   return 0;
 }
@@ -1582,9 +1586,35 @@ int dsr_frame_inputs_host(const dsr_camera* cam, const dsr_frame_params* params,
   return 0;
 }
 
+int dsr_frame_pose_params_default(dsr_frame_pose_params* p) {
+  if (!p) return -2;
+  p->outlier_radius = 1.0f;
+  p->lo_pct = 5;
+  p->hi_pct = 95;
+  p->box_margin = 1.2f;
+  p->scale_factor = 0.40f;
+  p->min_points = 50;
+  p->up[0] = 0.f;
+  p->up[1] = -1.f;
+  p->up[2] = 0.f;
+  return 0;
+}
+
+int dsr_frame_poses_host(const dsr_camera* cam, const dsr_frame_params* params,
+                         const dsr_frame_pose_params* pose_params, const float* depth, const int* instance,
+                         int n_det, const dsr_frame_det* dets, const int* modes, float* pts, float* rays,
+                         float* dobs, dsr_frame_det_out* out, dsr_frame_pose_out* pose_out) {
+  if (frame_args_error(cam, params, depth, instance, n_det, dets)) return -2;
+  if (frame_pose_args_error(pose_params, n_det, modes)) return -2;
+  if (n_det > 0 && (!pts || !rays || !dobs || !out || !pose_out)) return -2;
+  frame_poses_host_impl(frame_cam(cam), *params, *pose_params, depth, instance, n_det, dets, modes, pts, rays, dobs,
+                        out, pose_out);
+  return 0;
+}
+
 // the uploaded part of a frame block: depth | instance | detections, laid out as frame_carve does
 static void frame_pack(void* host, const dsr_camera* cam, const float* depth, const int* inst, int n_det,
-                       const dsr_frame_det* dets) {
+                       const dsr_frame_det* dets, const int* modes = nullptr) {
   const FrameDev H = frame_carve(host, cam->width, cam->height, n_det);
   const size_t px = (size_t)cam->width * cam->height;
   std::memcpy(H.depth, depth, px * sizeof(float));
@@ -1592,6 +1622,7 @@ static void frame_pack(void* host, const dsr_camera* cam, const float* depth, co
   for (int d = 0; d < n_det; ++d) {
     H.dets[d].label = dets[d].label;
     for (int k = 0; k < 4; ++k) H.dets[d].bbox[k] = dets[d].bbox[k];
+    H.dets[d].mode = modes ? modes[d] : DSR_FRAME_POSE_GIVEN;
   }
 }
 
@@ -1644,12 +1675,16 @@ int dsr_frame_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params
   return rc;
 }
 
-int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
-                           const float* depth, const int* instance, int n_det, const dsr_frame_det* dets) {
+// dsr_batch_refill_frame (pose_params == null) and dsr_batch_refill_frame_poses
+static int batch_refill_frame_impl(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                                   const dsr_frame_pose_params* pose_params, const float* depth,
+                                   const int* instance, int n_det, const dsr_frame_det* dets, const int* modes) {
   if (!b) return -2;
   dsr_ctx* ctx = b->ctx;
   if (!b->capacity) return fail(ctx, "dsr_batch_refill_frame needs a batch from dsr_batch_create_capacity");
   if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
+  if (pose_params)
+    if (const char* m = frame_pose_args_error(pose_params, n_det, modes)) return fail(ctx, m);
   if (n_det > b->n_obj) return fail(ctx, "refill_frame: n_det exceeds the batch's object capacity");
   if (params->max_pts > b->max_pts) return fail(ctx, "refill_frame: max_pts exceeds the batch's max_pts");
   if ((long long)params->max_pts + params->max_bg > b->max_rays)
@@ -1659,7 +1694,8 @@ int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_
   // the previous refill's copies read the staging buffers until they complete
   DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
   const int W = cam->width, H = cam->height;
-  const size_t up = frame_upload_bytes(W, H, n_det), all = frame_dev_bytes(W, H, n_det);
+  const size_t up = frame_upload_bytes(W, H, n_det),
+               all = frame_dev_bytes(W, H, n_det) + (pose_params ? frame_pose_dev_bytes(n_det, params->max_pts) : 0);
   hipStream_t s = ctx->stream;
   if (up > b->frame_host_bytes) {
     if (b->frame_host) hipHostFree(b->frame_host);
@@ -1677,7 +1713,7 @@ int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_
     DSR_CHECK(ctx, hipMalloc(&b->frame_dev, all));
     b->frame_dev_bytes = all;
   }
-  frame_pack(b->frame_host, cam, depth, instance, n_det, dets);
+  frame_pack(b->frame_host, cam, depth, instance, n_det, dets, pose_params ? modes : nullptr);
   auto* desc = static_cast<ObjDesc*>(b->stage[0].host);
   auto* t_in = static_cast<float*>(b->stage[1].host);
   auto* z_in = static_cast<float*>(b->stage[2].host);
@@ -1687,19 +1723,25 @@ int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_
     d.n_pts = d.n_rays = d.n_fg = 0;
     desc[o] = d;
     const dsr_frame_det* x = o < n_det ? &dets[o] : nullptr;
+    // a cuboid detection's pose row is written by k_frame_pose after this upload (t_cam_obj)
+    const bool given = x && !(pose_params && modes[o] != DSR_FRAME_POSE_GIVEN);
     float* t = t_in + (size_t)o * 16;
-    for (int i = 0; i < 16; ++i) t[i] = x ? x->t_cam_obj[i] : (i % 5 == 0 ? 1.f : 0.f);
+    for (int i = 0; i < 16; ++i) t[i] = given ? x->t_cam_obj[i] : (i % 5 == 0 ? 1.f : 0.f);
     float* z = z_in + (size_t)o * CODE;
     std::memset(z, 0, sizeof(float) * CODE);
     if (x && x->code) std::memcpy(z, x->code, sizeof(float) * b->dec->code_len);
-    is_oc[o] = (x && x->pose_is_obj_cam) ? 1 : 0;
+    is_oc[o] = (given && x->pose_is_obj_cam) ? 1 : 0;
   }
   for (int k = 0; k < 4; ++k)                      // desc, t_in, z_in, is_oc (pts / rays / dobs: the kernels)
     DSR_CHECK(ctx, hipMemcpyAsync(b->stage[k].dev, b->stage[k].host, b->stage[k].bytes, hipMemcpyHostToDevice, s));
   DSR_CHECK(ctx, hipMemcpyAsync(b->frame_dev, b->frame_host, up, hipMemcpyHostToDevice, s));
   if (n_det > 0) {
-    frame_launch(s, frame_cam(cam), *params, n_det, frame_carve(b->frame_dev, W, H, n_det), b->desc, b->pts,
-                 b->rays, b->dobs);
+    const FrameDev D = frame_carve(b->frame_dev, W, H, n_det);
+    frame_launch(s, frame_cam(cam), *params, n_det, D, b->desc, b->pts, b->rays, b->dobs);
+    if (pose_params)
+      frame_pose_launch(s, *params, *pose_params, n_det, D,
+                        frame_pose_carve(b->frame_dev, W, H, n_det, params->max_pts), b->desc, b->pts, b->rays,
+                        b->dobs, b->t_in);
     DSR_CHECK(ctx, hipGetLastError());
   }
   if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
@@ -1708,7 +1750,95 @@ int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_
   b->frame_n = n_det;
   b->frame_w = W;
   b->frame_h = H;
+  b->frame_pose_pts = pose_params ? params->max_pts : -1;
   b->ran = false;
+  return 0;
+}
+
+// dsr_frame_inputs plus k_frame_pose / k_frame_compact; the given poses travel in a t_in array
+int dsr_frame_poses(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params,
+                    const dsr_frame_pose_params* pose_params, const float* depth, const int* instance,
+                    int n_det, const dsr_frame_det* dets, const int* modes, float* pts, float* rays,
+                    float* dobs, dsr_frame_det_out* out, dsr_frame_pose_out* pose_out) {
+  if (!ctx) return -2;
+  if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
+  if (const char* m = frame_pose_args_error(pose_params, n_det, modes)) return fail(ctx, m);
+  if (n_det > 0 && (!pts || !rays || !dobs || !out || !pose_out)) return fail(ctx, "frame: null output arrays");
+  if (n_det == 0) return 0;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const int W = cam->width, H = cam->height;
+  const size_t up = frame_upload_bytes(W, H, n_det),
+               all = frame_dev_bytes(W, H, n_det) + frame_pose_dev_bytes(n_det, params->max_pts);
+  const size_t np = (size_t)n_det * params->max_pts * 3, nr = (size_t)n_det * ((size_t)params->max_pts + params->max_bg) * 3,
+               nz = (size_t)n_det * params->max_pts, nt = (size_t)n_det * 16;
+  std::vector<char> host(up);
+  frame_pack(host.data(), cam, depth, instance, n_det, dets, modes);
+  std::vector<float> tin(nt);
+  for (int d = 0; d < n_det; ++d)
+    for (int i = 0; i < 16; ++i) tin[(size_t)d * 16 + i] = dets[d].t_cam_obj[i];
+  char* dev = nullptr;
+  float* o = nullptr;                            // pts | rays | dobs | t_in
+  hipStream_t s = ctx->stream;
+  int rc = 0;
+  auto chk = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == 0) {
+      ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+      rc = -1;
+    }
+    return e == hipSuccess;
+  };
+  if (chk(hipMalloc((void**)&dev, all), "hipMalloc (frame)") &&
+      chk(hipMalloc((void**)&o, sizeof(float) * (np + nr + nz + nt)), "hipMalloc (frame outputs)")) {
+    const FrameDev D = frame_carve(dev, W, H, n_det);
+    const FramePoseDev E = frame_pose_carve(dev, W, H, n_det, params->max_pts);
+    chk(hipMemcpyAsync(dev, host.data(), up, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o, pts, sizeof(float) * np, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o + np, rays, sizeof(float) * nr, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o + np + nr, dobs, sizeof(float) * nz, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o + np + nr + nz, tin.data(), sizeof(float) * nt, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    if (rc == 0) {
+      frame_launch(s, frame_cam(cam), *params, n_det, D, nullptr, o, o + np, o + np + nr);
+      frame_pose_launch(s, *params, *pose_params, n_det, D, E, nullptr, o, o + np, o + np + nr, o + np + nr + nz);
+      chk(hipGetLastError(), "frame kernels");
+      chk(hipMemcpyAsync(pts, o, sizeof(float) * np, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(rays, o + np, sizeof(float) * nr, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(dobs, o + np + nr, sizeof(float) * nz, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(out, D.recs, sizeof(dsr_frame_det_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(pose_out, E.precs, sizeof(dsr_frame_pose_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+    }
+    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
+  }
+  if (o) hipFree(o);
+  if (dev) hipFree(dev);
+  return rc;
+}
+
+int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                           const float* depth, const int* instance, int n_det, const dsr_frame_det* dets) {
+  return batch_refill_frame_impl(b, cam, params, nullptr, depth, instance, n_det, dets, nullptr);
+}
+
+int dsr_batch_refill_frame_poses(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                                 const dsr_frame_pose_params* pose_params, const float* depth,
+                                 const int* instance, int n_det, const dsr_frame_det* dets, const int* modes) {
+  if (!b) return -2;
+  if (!pose_params) return fail(b->ctx, "frame poses: null pose parameters");
+  return batch_refill_frame_impl(b, cam, params, pose_params, depth, instance, n_det, dets, modes);
+}
+
+int dsr_batch_frame_pose_info(dsr_batch* b, dsr_frame_pose_out* out) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  if (b->frame_n < 0 || b->frame_pose_pts < 0)
+    return fail(ctx, "dsr_batch_frame_pose_info: the batch's last fill was not a frame with poses (dsr_batch_refill_frame_poses)");
+  if (b->frame_n == 0) return 0;
+  if (!out) return fail(ctx, "null argument");
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+  const FramePoseDev E = frame_pose_carve(b->frame_dev, b->frame_w, b->frame_h, b->frame_n, b->frame_pose_pts);
+  DSR_CHECK(ctx, hipMemcpy(out, E.precs, sizeof(dsr_frame_pose_out) * b->frame_n, hipMemcpyDeviceToHost));
   return 0;
 }
 

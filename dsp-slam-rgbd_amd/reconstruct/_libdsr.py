@@ -194,6 +194,26 @@ FRAME_STATUS = {0: "ok", 1: "no pixel carries the label", 2: "mask of at most mi
                 3: "no valid depth in the mask"}
 
 
+class FramePoseParams(C.Structure):
+    """dsr_frame_pose_params: every value is taken literally (dsr_frame_pose_params_default fills the
+    reference's constants)."""
+    _fields_ = [("outlier_radius", C.c_float), ("lo_pct", C.c_int), ("hi_pct", C.c_int), ("box_margin", C.c_float),
+                ("scale_factor", C.c_float), ("min_points", C.c_int), ("up", C.c_float * 3)]
+
+
+class FramePoseOut(C.Structure):
+    """dsr_frame_pose_out: the start-pose record of one detection."""
+    _fields_ = [("status", C.c_int), ("n_in", C.c_int), ("n_near", C.c_int), ("n_kept", C.c_int),
+                ("dims", C.c_double * 3), ("eig", C.c_double * 3), ("t_cam_obj", C.c_float * 16)]
+
+
+FRAME_POSE_GIVEN, FRAME_POSE_CUBOID, FRAME_POSE_CUBOID_FLIPPED = 0, 1, 2   # include/dsr.h, the modes
+# include/dsr.h DSR_FRAME_POSE_* statuses
+FRAME_POSE_OK, FRAME_POSE_NOT_ASKED, FRAME_POSE_NO_INPUT, FRAME_POSE_FEW_POINTS, FRAME_POSE_DEGENERATE = 0, 1, 2, 3, 4
+FRAME_POSE_STATUS = {0: "ok", 1: "not asked (the detection brought its pose)", 2: "no input (the ingest is not ok)",
+                     3: "fewer than min_points points", 4: "degenerate cuboid (l == 0 or a non-finite value)"}
+
+
 #: dsr_batch_lite_diag record layout (csrc/dsr_dev.hpp: STD_*)
 LITE_DIAG_FIELDS = ("broken_blocks", "recorded", "block", "wave", "counter", "target", "observed", "tile_iter",
                     "hw_id", "xcc_id", "polls", "real_ticks")
@@ -273,6 +293,16 @@ SIGNATURES = {
     "dsr_batch_refill_frame": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams), FP, IP, C.c_int,
                                          C.POINTER(FrameDet)]),
     "dsr_batch_frame_info": (C.c_int, [C.c_void_p, C.POINTER(FrameDetOut)]),
+    "dsr_frame_pose_params_default": (C.c_int, [C.POINTER(FramePoseParams)]),
+    "dsr_frame_poses_host": (C.c_int, [C.POINTER(Camera), C.POINTER(FrameParams), C.POINTER(FramePoseParams), FP, IP,
+                                       C.c_int, C.POINTER(FrameDet), IP, FP, FP, FP, C.POINTER(FrameDetOut),
+                                       C.POINTER(FramePoseOut)]),
+    "dsr_frame_poses": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams), C.POINTER(FramePoseParams),
+                                  FP, IP, C.c_int, C.POINTER(FrameDet), IP, FP, FP, FP, C.POINTER(FrameDetOut),
+                                  C.POINTER(FramePoseOut)]),
+    "dsr_batch_refill_frame_poses": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams),
+                                               C.POINTER(FramePoseParams), FP, IP, C.c_int, C.POINTER(FrameDet), IP]),
+    "dsr_batch_frame_pose_info": (C.c_int, [C.c_void_p, C.POINTER(FramePoseOut)]),
 }
 
 #: entry points added without an ABI number change: callers detect them by the symbol, so a
@@ -281,7 +311,8 @@ BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_rende
              "dsr_renderer_destroy", "dsr_render_layout", "dsr_frame_params_default", "dsr_frame_inputs_host",
              "dsr_frame_inputs", "dsr_batch_refill_frame", "dsr_batch_frame_info", "dsr_scene_create",
              "dsr_scene_set_objects", "dsr_scene_query", "dsr_scene_peek", "dsr_scene_stats_get", "dsr_scene_destroy",
-             "dsr_scene_bin_host")
+             "dsr_scene_bin_host", "dsr_frame_pose_params_default", "dsr_frame_poses_host", "dsr_frame_poses",
+             "dsr_batch_refill_frame_poses", "dsr_batch_frame_pose_info")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

@@ -276,7 +276,7 @@ class Optimizer(object):
             res[i]["vertices"], res[i]["faces"] = mesh.vertices, mesh.faces
         return res
 
-    def reconstruct_frame(self, depth, instance, detections, camera, mesher=None, **params):
+    def reconstruct_frame(self, depth, instance, detections, camera, mesher=None, pose_params=None, **params):
         """One keyframe straight from a depth image and an instance-label image (the format
         ``SdfRenderer.render`` emits): what ``reconstruct_keyframe`` returns for the inputs
         ``reconstruct.utils.frame_inputs`` builds, without building them on the host.  The images
@@ -290,44 +290,92 @@ class Optimizer(object):
         ``params``: ``utils.FRAME_PARAM_NAMES`` (the slot's capacity comes from max_pts / max_bg).
         Every result carries the detection's ingest record as ``ingest``.  With ``keyframe_mode``
         "oneshot", or when no slot is within the capacity bounds, the inputs are built on the host
-        (``frame_inputs``) and run through ``reconstruct_keyframe``."""
+        (``frame_inputs``) and run through ``reconstruct_keyframe``.
+
+        A detection without ``t_cam_obj`` (or with ``None``) — the reference's mono / RGB-D call
+        site, LocalMapping_util.cc:284-410, where no 3-D detector supplies a pose — starts from the
+        PCA cuboid of its own points with the outliers of ``MapObject::RemoveOutliersSimple`` /
+        ``ComputeCuboidPCA_onlyformono`` (MapObject.cc:249-283, :330-443) left out, computed on the
+        device after the ingest (dsr_batch_refill_frame_poses; the rule is DESIGN.md §3.5c); with
+        ``reconstructed=False`` its duplicate is the cuboid-flipped mode, flipped on the device.
+        ``pose_params``: a dict over ``utils.FRAME_POSE_PARAM_NAMES``.  Every result carries the
+        pose record as ``pose_init`` (``utils.frame_pose_record``) beside ``ingest``; when every
+        detection brings a pose the call goes through dsr_batch_refill_frame exactly as before.
+        The fallback then runs ``utils.frame_poses`` + ``reconstruct_keyframe``: bitwise the same
+        results."""
         from reconstruct import utils as U
 
         cam = U.frame_camera(camera)
         p = U.frame_params(**params)
         depth, instance = U.frame_images(depth, instance, cam)
+        poses = any(det.get("t_cam_obj") is None for det in detections)
+        q = U.frame_pose_params(pose_params) if poses or pose_params is not None else None
         hyp, pairs = [], []
         for det in detections:
             i, j = len(hyp), None
-            hyp.append(det)
+            cuboid = det.get("t_cam_obj") is None
+            hyp.append(dict(det, mode=L.FRAME_POSE_CUBOID) if cuboid else dict(det, mode=None))
             if not det.get("reconstructed", True):
                 j = len(hyp)
-                hyp.append(dict(det, t_cam_obj=np.asarray(det["t_cam_obj"], np.float32).reshape(4, 4) @ FLIP))
+                if cuboid:
+                    hyp.append(dict(det, mode=L.FRAME_POSE_CUBOID_FLIPPED))
+                else:
+                    hyp.append(dict(det, mode=None,
+                                    t_cam_obj=np.asarray(det["t_cam_obj"], np.float32).reshape(4, 4) @ FLIP))
             pairs.append((i, j))
         n = len(hyp)
         if n == 0:
             return []
         ctx = self._ctx
+        if poses and not hasattr(ctx.lib, "dsr_batch_refill_frame_poses"):
+            raise L.DsrError("this libdsr has no dsr_batch_refill_frame_poses: detections without t_cam_obj need it")
+
+        def given_record(h, ingest):
+            return ForceKeyErrorDict(status=L.FRAME_POSE_NOT_ASKED, n_in=ingest.n_pts, n_near=0, n_kept=0,
+                                     dims=np.zeros(3), eig=np.zeros(3),
+                                     t_cam_obj=np.asarray(h["t_cam_obj"], np.float32).reshape(4, 4).copy())
+
         slot = None
         if hasattr(ctx.lib, "dsr_batch_refill_frame") and p.max_pts >= 1 and p.max_bg >= 0:
             slot = self._slot_for_caps(n, p.max_pts, p.max_pts + p.max_bg, n * (p.max_pts + p.max_bg))
-        if slot is None:
+        if slot is None and not poses:
             objects, records = U.frame_inputs(depth, instance, detections, cam, **params)
             res = self.reconstruct_keyframe([ob + (det.get("reconstructed", True),)
                                              for ob, det in zip(objects, detections)], mesher)
-            for r, rec in zip(res, records):
+            for r, rec, det in zip(res, records, detections):
                 r["ingest"] = rec
+                r["pose_init"] = given_record(det, rec)
             return res
-        dets, keep = U.frame_dets(hyp, self.code_len)
+        if slot is None:                                       # host twin, every hypothesis its own object
+            objects, records, precs = U.frame_poses(depth, instance, hyp, cam, q, **params)
+            runs = self.reconstruct_keyframe([ob + (True,) for ob in objects])
+            res = []
+            for i, j in pairs:
+                k = i
+                if j is not None and float(runs[i]["loss"]) > float(runs[j]["loss"]):
+                    k = j
+                r = runs[k]
+                r["ingest"], r["pose_init"] = records[k], precs[k]
+                res.append(r)
+            return self._mesh_results(res, mesher)
+        dets, keep = U.frame_dets([U._with_pose(h) for h in hyp], self.code_len)
         outs = (L.ObjectOut * n)()
         recs = (L.FrameDetOut * n)()
-        ctx.check(ctx.lib.dsr_batch_refill_frame(slot.handle, cam, p, L.fptr(depth), L.iptr(instance), n, dets),
-                  "dsr_batch_refill_frame")
+        precs = (L.FramePoseOut * n)()
+        if poses:
+            modes = U.frame_pose_modes(hyp)
+            ctx.check(ctx.lib.dsr_batch_refill_frame_poses(slot.handle, cam, p, q, L.fptr(depth), L.iptr(instance), n,
+                                                           dets, L.iptr(modes)), "dsr_batch_refill_frame_poses")
+        else:
+            ctx.check(ctx.lib.dsr_batch_refill_frame(slot.handle, cam, p, L.fptr(depth), L.iptr(instance), n, dets),
+                      "dsr_batch_refill_frame")
         slot.busy = True
         try:
             ctx.check(ctx.lib.dsr_batch_run(slot.handle), "dsr_batch_run")
             ctx.check(ctx.lib.dsr_batch_download(slot.handle, outs), "dsr_batch_download")
             ctx.check(ctx.lib.dsr_batch_frame_info(slot.handle, recs), "dsr_batch_frame_info")
+            if poses:
+                ctx.check(ctx.lib.dsr_batch_frame_pose_info(slot.handle, precs), "dsr_batch_frame_pose_info")
         finally:
             slot.busy = False
         res = []
@@ -339,6 +387,7 @@ class Optimizer(object):
             r["iters_done"] = int(outs[k].iters_done)
             r["fail_reason"] = L.FAIL_REASONS.get(int(outs[k].fail_reason), "?")
             r["ingest"] = U.frame_record(recs[k])
+            r["pose_init"] = U.frame_pose_record(precs[k]) if poses else given_record(hyp[k], r["ingest"])
             res.append(r)
         return self._mesh_results(res, mesher)
 

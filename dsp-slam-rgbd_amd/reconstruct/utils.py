@@ -233,6 +233,102 @@ def frame_inputs(depth, instance, detections, camera, **params):
     return objects, records
 
 
+FRAME_POSE_PARAM_NAMES = ("outlier_radius", "lo_pct", "hi_pct", "box_margin", "scale_factor", "min_points", "up")
+
+
+def frame_pose_params(pose_params=None):
+    """``dsr_frame_pose_params``: the reference's constants (dsr_frame_pose_params_default:
+    outlier_radius 1.0, lo_pct 5, hi_pct 95, box_margin 1.2, scale_factor 0.40, min_points 50, up
+    (0, -1, 0); MapObject.cc:278, :380, :387-388, :410, :437, LocalMapping_util.cc:333) with the
+    dict ``pose_params`` on top; a ``_libdsr.FramePoseParams`` is passed through."""
+    from reconstruct import _libdsr as L
+
+    if isinstance(pose_params, L.FramePoseParams):
+        return pose_params
+    pose_params = dict(pose_params or {})
+    unknown = set(pose_params) - set(FRAME_POSE_PARAM_NAMES)
+    if unknown:
+        raise TypeError(f"unknown frame pose parameters: {sorted(unknown)}")
+    p = L.FramePoseParams()
+    if L.load_library().dsr_frame_pose_params_default(p) != 0:
+        raise L.DsrError("dsr_frame_pose_params_default failed")
+    for k, v in pose_params.items():
+        if k == "up":
+            p.up[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, int(v) if k in ("lo_pct", "hi_pct", "min_points") else float(v))
+    return p
+
+
+def frame_pose_modes(detections):
+    """Per detection its pose mode (include/dsr.h DSR_FRAME_POSE_*): ``mode`` if the dict carries
+    one, else given when it brings a ``t_cam_obj``, else cuboid."""
+    from reconstruct import _libdsr as L
+
+    return np.asarray([int(d["mode"]) if d.get("mode") is not None else
+                       (L.FRAME_POSE_GIVEN if d.get("t_cam_obj") is not None else L.FRAME_POSE_CUBOID)
+                       for d in detections], np.int32).reshape(-1)
+
+
+def frame_pose_record(o):
+    """A ``dsr_frame_pose_out`` as a dict."""
+    return ForceKeyErrorDict(status=int(o.status), n_in=int(o.n_in), n_near=int(o.n_near), n_kept=int(o.n_kept),
+                             dims=np.array(o.dims[:], np.float64), eig=np.array(o.eig[:], np.float64),
+                             t_cam_obj=np.array(o.t_cam_obj[:], np.float32).reshape(4, 4))
+
+
+def _with_pose(det):
+    return det if det.get("t_cam_obj") is not None else dict(det, t_cam_obj=np.eye(4, dtype=np.float32))
+
+
+def frame_poses(depth, instance, detections, camera, pose_params=None, **params):
+    """``frame_inputs`` for detections that may come without a pose — the reference's mono / RGB-D
+    call site (LocalMapping_util.cc:284-410): ``MapObject::RemoveOutliersSimple`` and
+    ``ComputeCuboidPCA_onlyformono`` (MapObject.cc:249-283, :330-443) give the start pose and the
+    points / rays that survive, by the exact rule of DESIGN.md §3.5c (``dsr_frame_poses_host``:
+    plain C++ on the host, no device).  A detection without ``t_cam_obj`` (or with ``None``) gets
+    the cuboid pose; ``mode`` (``_libdsr.FRAME_POSE_*``) overrides that, e.g. the flipped cuboid.
+    ``pose_params``: a dict over ``FRAME_POSE_PARAM_NAMES`` (see ``frame_pose_params``).  Returns
+    ``(objects, records, pose_records)``: objects as ``frame_inputs`` with the start pose and the
+    kept rows, the ingest records, and the pose records (``frame_pose_record``).  A detection
+    without a start pose has empty arrays and the identity."""
+    from reconstruct import _libdsr as L
+
+    lib = L.load_library()
+    cam = frame_camera(camera)
+    p = frame_params(**params)
+    q = frame_pose_params(pose_params)
+    depth, instance = frame_images(depth, instance, cam)
+    n = len(detections)
+    modes = frame_pose_modes(detections)
+    dets, keep = frame_dets([_with_pose(d) for d in detections])
+    mp, mr = max(p.max_pts, 0), max(p.max_pts, 0) + max(p.max_bg, 0)
+    pts = np.zeros((max(n, 1), mp, 3), np.float32)
+    rays = np.zeros((max(n, 1), mr, 3), np.float32)
+    dobs = np.zeros((max(n, 1), mp), np.float32)
+    out = (L.FrameDetOut * max(n, 1))()
+    pout = (L.FramePoseOut * max(n, 1))()
+    rc = lib.dsr_frame_poses_host(cam, p, q, L.fptr(depth), L.iptr(instance), n, dets, L.iptr(modes), L.fptr(pts),
+                                  L.fptr(rays), L.fptr(dobs), out, pout)
+    if rc != 0:
+        raise L.DsrError(f"dsr_frame_poses_host failed ({rc}): bad camera, image, frame or pose parameters")
+    objects, records, poses = [], [], []
+    for i, det in enumerate(detections):
+        r, pr = frame_record(out[i]), frame_pose_record(pout[i])
+        if pr.status == L.FRAME_POSE_NOT_ASKED:
+            n_p, n_r = r.n_pts, r.n_pts + r.n_bg
+        elif pr.status == L.FRAME_POSE_OK:
+            n_p, n_r = pr.n_kept, pr.n_kept + r.n_bg
+        else:
+            n_p = n_r = 0
+        code = det.get("code")
+        objects.append((pr.t_cam_obj.copy(), pts[i, :n_p].copy(), rays[i, :n_r].copy(), dobs[i, :n_p].copy(),
+                        None if code is None else np.asarray(code, np.float32)))
+        records.append(r)
+        poses.append(pr)
+    return objects, records, poses
+
+
 def create_voxel_grid(vol_dim=128):
     """utils.py:97-116.  Note the reference's ``LongTensor / vol_dim`` is TRUE division
     in torch >= 1.6 (fp32), so its x/y columns are not integer lattice indices; this

@@ -635,6 +635,96 @@ int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_
  * batch's last fill was not a frame. */
 int dsr_batch_frame_info(dsr_batch* b, dsr_frame_det_out* out);
 
+/* ---- frame ingest with cuboid start poses and outlier removal (DESIGN.md 3.5c states the rule
+ * exactly; callers detect these entry points by symbol, the ABI number is unchanged).  On the
+ * reference's mono / RGB-D path no 3-D detector supplies t_cam_obj; the start pose comes from the
+ * object's own 3-D points: MapObject::RemoveOutliersSimple (src/MapObject.cc:249-283) drops points
+ * farther than 1.0 from their mean, MapObject::ComputeCuboidPCA_onlyformono (src/MapObject.cc:330-443)
+ * builds a PCA cuboid with 5 % / 95 % extents, flags the points outside 1.2 x the box and sets the
+ * pose to 0.40 l R | centre, and LocalMapping_util.cc:284-410 leaves the flagged points out of
+ * surface_points_cam and the rays, starts reconstruct_object from that pose and, for an object
+ * not yet reconstructed, again from the flipped pose (flipped_Two, :402-404).  Here that runs per
+ * detection on the rows the ingest above produced, in fp64 on the fp32 rows, every operation
+ * rounded individually, sums in one fixed shape (256 strided partials added in index order), so
+ * host, device and the numpy restatement agree bitwise.  Out of scope: RemoveOutliersModel
+ * (src/MapObject.cc:285-328), occlusion masks, per-class scale factors. */
+typedef struct {
+  float outlier_radius;           /* pass 1: points farther than this from their mean are dropped
+                                     (1.0, MapObject.cc:278); +inf switches the pass off */
+  int lo_pct, hi_pct;             /* extents: order statistics at ranks (n lo_pct)/100 and
+                                     (n hi_pct)/100, integer division (5, 95; MapObject.cc:387-388) */
+  float box_margin;               /* pass 2: points outside box_margin x the box are dropped
+                                     (1.2, MapObject.cc:410); +inf switches the pass off */
+  float scale_factor;             /* pose scale = scale_factor x l (0.40, MapObject.cc:437) */
+  int min_points;                 /* fewer points at any stage: no start pose (50,
+                                     LocalMapping_util.cc:333) */
+  float up[3];                    /* the camera-frame direction column 1 of R must not oppose
+                                     ((0, -1, 0), MapObject.cc:380) */
+} dsr_frame_pose_params;
+enum {                            /* where a detection's start pose comes from */
+  DSR_FRAME_POSE_GIVEN = 0,       /* its t_cam_obj: exactly a detection of dsr_batch_refill_frame */
+  DSR_FRAME_POSE_CUBOID = 1,      /* the PCA cuboid of its points (MapObject.cc:330-443) */
+  DSR_FRAME_POSE_CUBOID_FLIPPED = 2 /* that pose with columns 0 and 2 negated (LocalMapping_util.cc:402-404) */
+};
+enum {
+  DSR_FRAME_POSE_OK = 0,
+  DSR_FRAME_POSE_NOT_ASKED = 1,   /* mode DSR_FRAME_POSE_GIVEN */
+  DSR_FRAME_POSE_NO_INPUT = 2,    /* the ingest status is not DSR_FRAME_OK */
+  DSR_FRAME_POSE_FEW_POINTS = 3,  /* n_in, n_near or n_kept below min_points */
+  DSR_FRAME_POSE_DEGENERATE = 4   /* l == 0 or a non-finite value */
+};
+typedef struct {
+  int status;                     /* DSR_FRAME_POSE_* */
+  int n_in;                       /* the ingest's n_pts */
+  int n_near;                     /* after pass 1 (0 unless asked and the ingest is OK) */
+  int n_kept;                     /* after pass 2 (0 before that stage is reached) */
+  double dims[3];                 /* w, h, l (0 before that stage is reached) */
+  double eig[3];                  /* eigenvalues of the scatter matrix, ascending (0 before ...) */
+  float t_cam_obj[16];            /* the start pose handed to the run: the cuboid's (OK), the
+                                     detection's own (NOT_ASKED), else the identity */
+} dsr_frame_pose_out;
+
+/* Host only: outlier_radius 1.0, lo_pct 5, hi_pct 95, box_margin 1.2, scale_factor 0.40,
+ * min_points 50, up (0, -1, 0): the reference's constants (MapObject.cc:278, :380, :387-388, :410,
+ * :437; LocalMapping_util.cc:333).  The other calls take every value literally. */
+int dsr_frame_pose_params_default(dsr_frame_pose_params* p);
+/* dsr_frame_inputs_host, then the rule of DESIGN.md 3.5c per detection (RemoveOutliersSimple +
+ * ComputeCuboidPCA_onlyformono + the point / ray filtering of LocalMapping_util.cc:284-410) in
+ * plain C++ — no context, no device.  modes: n_det DSR_FRAME_POSE_* values; the t_cam_obj of a
+ * cuboid detection is ignored.  Strides as dsr_frame_inputs_host; for an OK cuboid detection the
+ * first n_kept rows of pts / dobs / rays hold the kept points in order and the n_bg background
+ * rays follow at ray row n_kept; rows beyond the counted ones are unspecified.  out keeps
+ * describing the ingest; pose_out: n_det records.  Returns < 0 for the argument errors of
+ * dsr_frame_inputs_host, a null array, an unknown mode, min_points < 1, !(0 <= lo_pct < hi_pct <
+ * 100), a non-positive or NaN radius, margin or scale factor (+inf is allowed for radius and
+ * margin), a non-finite or zero up. */
+int dsr_frame_poses_host(const dsr_camera* cam, const dsr_frame_params* params,
+                         const dsr_frame_pose_params* pose_params, const float* depth, const int* instance,
+                         int n_det, const dsr_frame_det* dets, const int* modes, float* pts, float* rays,
+                         float* dobs, dsr_frame_det_out* out, dsr_frame_pose_out* pose_out);
+/* The same arrays and records produced by the device kernels (k_frame_* + k_frame_pose +
+ * k_frame_compact, csrc/dsr_frame.hpp) and copied back: bitwise those of dsr_frame_poses_host on
+ * every counted row (MapObject.cc:249-283, :330-443 as above). */
+int dsr_frame_poses(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params,
+                    const dsr_frame_pose_params* pose_params, const float* depth, const int* instance,
+                    int n_det, const dsr_frame_det* dets, const int* modes, float* pts, float* rays,
+                    float* dobs, dsr_frame_det_out* out, dsr_frame_pose_out* pose_out);
+/* dsr_batch_refill_frame plus the two kernels (the mono / RGB-D call site,
+ * LocalMapping_util.cc:284-410, without host arrays): slot i's rows are compacted in device
+ * memory, its counts become n_kept / n_kept + n_bg, and the t_in row of a cuboid detection is
+ * written by the device after the staged upload on the same stream (pose_is_obj_cam is ignored
+ * for it).  A detection without a start pose (NO_INPUT, FEW_POINTS, DEGENERATE) is an empty
+ * object.  No argument of the run changes, so a DSR_BATCH_GRAPH batch keeps replaying one graph.
+ * Errors, returned before the device is touched: those of dsr_batch_refill_frame, the parameter
+ * errors of dsr_frame_poses_host and an unknown mode. */
+int dsr_batch_refill_frame_poses(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                                 const dsr_frame_pose_params* pose_params, const float* depth,
+                                 const int* instance, int n_det, const dsr_frame_det* dets, const int* modes);
+/* Waits for the last dsr_batch_refill_frame_poses and copies its n_det pose records (what
+ * LocalMapping_util.cc:333 reports by skipping the object); an error when the batch's last fill
+ * was not of this kind.  dsr_batch_frame_info still returns the ingest records. */
+int dsr_batch_frame_pose_info(dsr_batch* b, dsr_frame_pose_out* out);
+
 /* ---- multi-GPU from one process: replaces the per-detection loop
  * LocalMapping_util.cc:165-206 spread over devices.  ctx[g] / dec[g] are one context and
  * its decoder per device; objects are LPT-partitioned (cost n_rays*M + n_pts), each
