@@ -358,6 +358,8 @@ static int fail(dsr_ctx* ctx, const std::string& m) {
   return -2;
 }
 
+#include "dsr_host.hpp"
+
 extern "C" {
 
 int dsr_abi_version(void) { return DSR_ABI_VERSION; }
@@ -1087,7 +1089,7 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
   if (p->num_depth_samples < 2 || p->num_depth_samples > MAXM)
     return fail(ctx, "num_depth_samples must be in [2, 64]");
   if (p->num_iterations < 0) return fail(ctx, "num_iterations < 0");
-  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, dec)) return rc;
   hipSetDevice(ctx->device);
   auto* b = new dsr_batch();
   b->ctx = ctx;
@@ -2664,6 +2666,12 @@ __global__ void k_fold_code(DevDecoder D, const float* __restrict__ z, float* __
   bias0f[n] = D.bias[0][n] + s0;
   bias4f[n] = D.bias[4][n] + s4;
 }
+// the bias folds of n codes (64 floats each, back to back) into b0 / b4 (HID floats each)
+static void fold_codes(hipStream_t s, const DevDecoder& D, const float* codes, int n, float* b0, float* b4) {
+  for (int i = 0; i < n; ++i)
+    hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, codes + (size_t)i * CODE, b0 + (size_t)i * HID,
+                       b4 + (size_t)i * HID);
+}
 
 // ------------------------------------------------------------------------------------
 // load-time qualification of the lite pass (include/dsr.h: dsr_decoder_info)
@@ -2730,16 +2738,7 @@ static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec) {
     for (int t = 0; t * TILE < n; ++t) te.push_back(Tile{c, 0, t * TILE, std::min(TILE, n - t * TILE)});
   }
   const int ntl = (int)tl.size(), nte = (int)te.size();
-  std::vector<void*> al;
-  auto A = [&](void** p, size_t bytes) {
-    if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-    al.push_back(*p);
-    return true;
-  };
-  struct Free {
-    std::vector<void*>& al;
-    ~Free() { for (void* p : al) hipFree(p); }
-  } guard{al};
+  DevArena mem;
   float4* dc = nullptr;
   float *dl = nullptr, *de = nullptr, *dz = nullptr, *db0 = nullptr, *db4 = nullptr;
   unsigned char* dref = nullptr;
@@ -2747,13 +2746,10 @@ static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec) {
   ObjDesc* ddesc = nullptr;
   ObjState* dst = nullptr;
   Tile *dtl = nullptr, *dte = nullptr;
-  if (!A((void**)&dc, sizeof(float4) * tot) || !A((void**)&dl, sizeof(float) * tot) ||
-      !A((void**)&de, sizeof(float) * tot) || !A((void**)&dz, sizeof(float) * hz.size()) ||
-      !A((void**)&db0, sizeof(float) * HID * nc) || !A((void**)&db4, sizeof(float) * HID * nc) ||
-      !A((void**)&dref, tot) || !A((void**)&ddead, sizeof(int) * tot) || !A((void**)&dntl, sizeof(int)) ||
-      !A((void**)&dnte, sizeof(int)) || !A((void**)&ddesc, sizeof(ObjDesc) * nc) ||
-      !A((void**)&dst, sizeof(ObjState) * nc) || !A((void**)&dtl, sizeof(Tile) * ntl) ||
-      !A((void**)&dte, sizeof(Tile) * nte))
+  if (!mem.alloc(&dc, tot) || !mem.alloc(&dl, tot) || !mem.alloc(&de, tot) || !mem.alloc(&dz, hz.size()) ||
+      !mem.alloc(&db0, HID * nc) || !mem.alloc(&db4, HID * nc) || !mem.alloc(&dref, tot) ||
+      !mem.alloc(&ddead, tot) || !mem.alloc(&dntl, 1) || !mem.alloc(&dnte, 1) || !mem.alloc(&ddesc, nc) ||
+      !mem.alloc(&dst, nc) || !mem.alloc(&dtl, ntl) || !mem.alloc(&dte, nte))
     return fail(ctx, "hipMalloc failed (lite qualification)");
   hipStream_t st = ctx->stream;
   DSR_CHECK(ctx, hipMemcpyAsync(dc, cand.data(), sizeof(float4) * tot, hipMemcpyHostToDevice, st));
@@ -2767,9 +2763,7 @@ static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec) {
   DSR_CHECK(ctx, hipMemsetAsync(dref, 0, tot, st));
   DSR_CHECK(ctx, hipMemsetAsync(ddead, 0, sizeof(int) * tot, st));
   const DevDecoder& D = dec->D;
-  for (int c = 0; c < nc; ++c)
-    hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, st, D, (const float*)dz + (size_t)c * CODE,
-                       db0 + (size_t)c * HID, db4 + (size_t)c * HID);
+  fold_codes(st, D, dz, nc, db0, db4);
   ErtArgs E{};
   E.dead = ddead;
   E.M = 1;
@@ -2782,15 +2776,13 @@ static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec) {
   E.audit_log2 = 7;
   E.perturb = 0.0f;
   E.diag = nullptr;
-  hipLaunchKernelGGL(lite_schedule().kernel, dim3(ctx->n_cu), dim3(512), 0, st, D, (const Tile*)dtl, (const int*)dntl,
-                     (const ObjDesc*)ddesc, (const float4*)dc, (const float*)db0, (const float*)db4, dl, E);
+  launch_lite(st, ctx->n_cu, D, {dtl, dntl, ddesc, dc, db0, db4, dl, E});
   // against the split-fp16 exact pass a lite batch runs (fwd_kernel(12)), whatever a test's
   // DSR_FWD_VARIANT selects: the XCD soft-sync variants (bit 0) need a sync counter this launch
   // has not got, and batches on them never run the lite pass anyway
-  hipLaunchKernelGGL(fwd_kernel(12), dim3(ctx->n_cu), dim3(512), 0, st, D, (const Tile*)dte,
-                     (const int*)dnte, (const ObjDesc*)ddesc, (const float4*)dc, (const float*)db0,
-                     (const float*)db4, de, (unsigned*)nullptr, ErtArgs{nullptr, 1, 0.f, nullptr, nullptr},
-                     MaskArgs{nullptr, nullptr, nullptr, nullptr});
+  FwdQuery exact{dte, dnte, ddesc, dc, db0, db4, de};
+  exact.kernel = fwd_kernel(12);
+  launch_fwd(st, ctx->n_cu, D, exact);
   DSR_CHECK(ctx, hipGetLastError());
   std::vector<float> yl(tot), ye(tot);
   DSR_CHECK(ctx, hipMemcpyAsync(yl.data(), dl, sizeof(float) * tot, hipMemcpyDeviceToHost, st));
@@ -2836,7 +2828,7 @@ struct dsr_mesher {
   dsr_ctx* ctx = nullptr;
   const dsr_decoder* dec = nullptr;
   int d = 0, n = 0, nt = 0;
-  std::vector<void*> allocs;
+  DevArena mem;
   float4* pts = nullptr;       // grid points (x,y,z, bits(index)), tile-padded
   Tile* tiles = nullptr;
   int* ntiles = nullptr;
@@ -2853,18 +2845,8 @@ int dsr_mesher_destroy(dsr_mesher* m) {
   if (!m) return 0;
   hipSetDevice(m->ctx->device);
   mesh_batch_free(m->mb);
-  for (void* p : m->allocs) hipFree(p);
   delete m;
   return 0;
-}
-
-static bool mesher_alloc(dsr_mesher* m, void** p, size_t bytes) {
-  if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  m->allocs.push_back(*p);
-  return true;
 }
 
 // The marching-cubes half of a mesher: the volume (tile-padded: the grid decode writes it) and
@@ -2872,13 +2854,10 @@ static bool mesher_alloc(dsr_mesher* m, void** p, size_t bytes) {
 static bool mesher_alloc_mc(dsr_mesher* m) {
   const int d = m->d, n = m->n, nc = (d - 1) * (d - 1) * (d - 1), ne = 3 * n;
   const int nb = (std::max(ne, nc) + MC_SCAN_BLOCK - 1) / MC_SCAN_BLOCK;
-  auto A = [&](void** p, size_t bytes) { return mesher_alloc(m, p, bytes); };
-  return A((void**)&m->vol, sizeof(float) * (size_t)m->nt * TILE) &&
-         A((void**)&m->flag, sizeof(int) * (size_t)ne) && A((void**)&m->vidx, sizeof(int) * (size_t)ne) &&
-         A((void**)&m->ntri, sizeof(int) * (size_t)nc) && A((void**)&m->toff, sizeof(int) * (size_t)nc) &&
-         A((void**)&m->bsum, sizeof(int) * (size_t)nb) && A((void**)&m->tot, sizeof(int) * 2) &&
-         A((void**)&m->verts, sizeof(float) * 3 * (size_t)ne) &&
-         A((void**)&m->faces, sizeof(int) * 3 * (size_t)DSR_MC_MAX_TRI * nc);
+  DevArena& M = m->mem;
+  return M.alloc(&m->vol, (size_t)m->nt * TILE) && M.alloc(&m->flag, ne) && M.alloc(&m->vidx, ne) &&
+         M.alloc(&m->ntri, nc) && M.alloc(&m->toff, nc) && M.alloc(&m->bsum, nb) && M.alloc(&m->tot, 2) &&
+         M.alloc(&m->verts, 3 * (size_t)ne) && M.alloc(&m->faces, 3 * (size_t)DSR_MC_MAX_TRI * nc);
 }
 
 int dsr_mesher_create(dsr_ctx* ctx, const dsr_decoder* dec, const float* grid_pts, int vol_dim,
@@ -2886,7 +2865,7 @@ int dsr_mesher_create(dsr_ctx* ctx, const dsr_decoder* dec, const float* grid_pt
   if (!ctx || !dec || !grid_pts || !out) return fail(ctx, "null argument");
   *out = nullptr;
   if (vol_dim < 2 || vol_dim > 512) return fail(ctx, "vol_dim must be in [2, 512]");
-  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, dec)) return rc;
   hipSetDevice(ctx->device);
   auto* m = new dsr_mesher();
   m->ctx = ctx;
@@ -2895,11 +2874,10 @@ int dsr_mesher_create(dsr_ctx* ctx, const dsr_decoder* dec, const float* grid_pt
   m->n = vol_dim * vol_dim * vol_dim;
   m->nt = (m->n + TILE - 1) / TILE;
   const int n = m->n, nt = m->nt;
-  auto A = [&](void** p, size_t bytes) { return mesher_alloc(m, p, bytes); };
-  if (!A((void**)&m->pts, sizeof(float4) * (size_t)nt * TILE) || !A((void**)&m->tiles, sizeof(Tile) * nt) ||
-      !A((void**)&m->ntiles, sizeof(int)) || !A((void**)&m->desc, sizeof(ObjDesc)) ||
-      !A((void**)&m->code, sizeof(float) * CODE) || !A((void**)&m->b0, sizeof(float) * HID) ||
-      !A((void**)&m->b4, sizeof(float) * HID) || !mesher_alloc_mc(m)) {
+  DevArena& M = m->mem;
+  if (!M.alloc(&m->pts, (size_t)nt * TILE) || !M.alloc(&m->tiles, nt) || !M.alloc(&m->ntiles, 1) ||
+      !M.alloc(&m->desc, 1) || !M.alloc(&m->code, CODE) || !M.alloc(&m->b0, HID) || !M.alloc(&m->b4, HID) ||
+      !mesher_alloc_mc(m)) {
     dsr_mesher_destroy(m);
     return fail(ctx, "hipMalloc failed (mesher)");
   }
@@ -2938,7 +2916,7 @@ int dsr_mesher_run(dsr_mesher* m, const float* code, float level, float* verts, 
                    int fcap, int* n_verts, int* n_faces) {
   if (!m || !code || !n_verts || !n_faces) return fail(m ? m->ctx : nullptr, "null argument");
   dsr_ctx* ctx = m->ctx;
-  if (!variant_kernels_ok(m->dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, m->dec)) return rc;
   hipSetDevice(ctx->device);
   hipStream_t s = ctx->stream;
   const DevDecoder& D = m->dec->D;
@@ -2946,11 +2924,8 @@ int dsr_mesher_run(dsr_mesher* m, const float* code, float level, float* verts, 
   std::memcpy(zc, code, sizeof(float) * m->dec->code_len);
   DSR_CHECK(ctx, hipMemcpyAsync(m->code, zc, sizeof(float) * CODE, hipMemcpyHostToDevice, s));
   DSR_CHECK(ctx, hipStreamSynchronize(s));          // (zc is on this stack frame)
-  hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, (const float*)m->code, m->b0, m->b4);
-  hipLaunchKernelGGL(fwd_kernel_for(D, query_fwd_variant()), dim3(std::min(ctx->n_cu, m->nt)), dim3(512), 0, s, D,
-                     (const Tile*)m->tiles, (const int*)m->ntiles, (const ObjDesc*)m->desc, (const float4*)m->pts,
-                     (const float*)m->b0, (const float*)m->b4, m->vol, (unsigned*)nullptr,
-                     ErtArgs{nullptr, 1, 0.f, nullptr, nullptr}, MaskArgs{nullptr, nullptr, nullptr, nullptr});
+  fold_codes(s, D, m->code, 1, m->b0, m->b4);
+  launch_fwd(s, std::min(ctx->n_cu, m->nt), D, {m->tiles, m->ntiles, m->desc, m->pts, m->b0, m->b4, m->vol});
   return mc_run(m, level, verts, vcap, faces, fcap, n_verts, n_faces);
 }
 
@@ -2994,13 +2969,10 @@ int dsr_mc_volume(dsr_ctx* ctx, const float* vol, int vol_dim, float level, floa
   m.d = vol_dim;
   m.n = vol_dim * vol_dim * vol_dim;
   m.nt = (m.n + TILE - 1) / TILE;
-  struct Free {       // the scratch lives for this call only
-    dsr_mesher* m;
-    ~Free() {
-      hipStreamSynchronize(m->ctx->stream);
-      for (void* p : m->allocs) hipFree(p);
-    }
-  } guard{&m};
+  struct Drain {      // the scratch lives for this call only: m's arena frees it once the stream is idle
+    hipStream_t s;
+    ~Drain() { hipStreamSynchronize(s); }
+  } drain{ctx->stream};
   if (!mesher_alloc_mc(&m)) return fail(ctx, "hipMalloc failed (marching cubes)");
   DSR_CHECK(ctx, hipMemcpyAsync(m.vol, vol, sizeof(float) * (size_t)m.n, hipMemcpyHostToDevice, ctx->stream));
   return mc_run(&m, level, verts, vcap, faces, fcap, n_verts, n_faces);
@@ -3021,7 +2993,7 @@ struct MeshBatch {
   int S = 0, np = 0, ntl = 0, n_rb = 0;
   int last_ns = 0;             // slots of the last pass (dsr_mesher_peek)
   bool last_sign = false;
-  std::vector<void*> allocs;
+  DevArena mem;
   float4* pts = nullptr;       // the grid, once per slot (the kernels index it by ObjDesc.cand_off)
   float *lite = nullptr, *vol = nullptr, *codes = nullptr, *b0 = nullptr, *b4 = nullptr, *verts = nullptr;
   unsigned char *refine = nullptr, *tflag = nullptr;
@@ -3043,7 +3015,6 @@ struct MeshBatch {
 
 static void mesh_batch_free(MeshBatch* b) {
   if (!b) return;
-  for (void* p : b->allocs) hipFree(p);
   for (hipEvent_t e : b->ev)
     if (e) hipEventDestroy(e);
   delete b;
@@ -3069,40 +3040,17 @@ static bool mesh_batch_alloc(dsr_mesher* m, int S) {
   b->ntl = ntl;
   b->n_rb = 2 * (S + 1) + MS_INTS + 4 + 3 * S + STD_INTS;
   const size_t nb = (Sz * std::max(fl, (size_t)std::max(nc, nt)) + MC_SCAN_BLOCK - 1) / MC_SCAN_BLOCK;
-  bool ok = true;
-  auto A = [&](void** p, size_t bytes) {
-    if (!ok) return;
-    if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) {
-      (void)hipGetLastError();
-      ok = false;
-      return;
-    }
-    b->allocs.push_back(*p);
-  };
-  A((void**)&b->pts, sizeof(float4) * Sz * np);
-  A((void**)&b->lite, sizeof(float) * Sz * np);
-  A((void**)&b->vol, sizeof(float) * Sz * np);
-  A((void**)&b->refine, Sz * np);
-  A((void**)&b->codes, sizeof(float) * Sz * CODE);
-  A((void**)&b->b0, sizeof(float) * Sz * HID);
-  A((void**)&b->b4, sizeof(float) * Sz * HID);
-  A((void**)&b->flag, sizeof(int) * Sz * fl);          // (the lite kernel's dead flags live here too)
-  A((void**)&b->vidx, sizeof(int) * Sz * 3 * n);
-  A((void**)&b->ntri, sizeof(int) * Sz * nc);
-  A((void**)&b->toff, sizeof(int) * Sz * nc);
-  A((void**)&b->bsum, sizeof(int) * nb);
-  A((void**)&b->verts, sizeof(float) * 3 * Sz * 3 * n);
-  A((void**)&b->faces, sizeof(int) * 3 * Sz * DSR_MC_MAX_TRI * nc);
-  A((void**)&b->tflag, Sz * nt);
-  A((void**)&b->tmark, sizeof(int) * Sz * nt);
-  A((void**)&b->tpos, sizeof(int) * Sz * nt);
-  A((void**)&b->ltiles, sizeof(Tile) * Sz * ntl);
-  A((void**)&b->atiles, sizeof(Tile) * Sz * nt);
-  A((void**)&b->etiles, sizeof(Tile) * Sz * nt);
-  A((void**)&b->rtiles, sizeof(Tile) * Sz * nt);
-  A((void**)&b->desc, sizeof(ObjDesc) * Sz);
-  A((void**)&b->st, sizeof(ObjState) * Sz);
-  A((void**)&b->rb, sizeof(int) * b->n_rb);
+  DevArena& M = b->mem;
+  bool ok = M.alloc(&b->pts, Sz * np) && M.alloc(&b->lite, Sz * np) && M.alloc(&b->vol, Sz * np) &&
+            M.alloc(&b->refine, Sz * np) && M.alloc(&b->codes, Sz * CODE) && M.alloc(&b->b0, Sz * HID) &&
+            M.alloc(&b->b4, Sz * HID) &&
+            M.alloc(&b->flag, Sz * fl) &&          // (the lite kernel's dead flags live here too)
+            M.alloc(&b->vidx, Sz * 3 * n) && M.alloc(&b->ntri, Sz * nc) && M.alloc(&b->toff, Sz * nc) &&
+            M.alloc(&b->bsum, nb) && M.alloc(&b->verts, 3 * Sz * 3 * n) &&
+            M.alloc(&b->faces, 3 * Sz * DSR_MC_MAX_TRI * nc) && M.alloc(&b->tflag, Sz * nt) &&
+            M.alloc(&b->tmark, Sz * nt) && M.alloc(&b->tpos, Sz * nt) && M.alloc(&b->ltiles, Sz * ntl) &&
+            M.alloc(&b->atiles, Sz * nt) && M.alloc(&b->etiles, Sz * nt) && M.alloc(&b->rtiles, Sz * nt) &&
+            M.alloc(&b->desc, Sz) && M.alloc(&b->st, Sz) && M.alloc(&b->rb, b->n_rb);
   for (hipEvent_t& e : b->ev)
     if (ok && hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; ok = false; }
   if (ok) {
@@ -3163,12 +3111,7 @@ static int mesh_pass(dsr_mesher* m, int ns, float level, bool sign, const ErtArg
   DSR_CHECK(ctx, hipMemcpyAsync(b->codes, b->hcodes.data(), sizeof(float) * CODE * ns, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_mesh_begin, dim3(1), dim3(256), 0, s, b->rb, b->n_rb, b->cnt, ns * b->ntl, ns * nt);
   DSR_CHECK(ctx, hipEventRecord(b->ev[0], s));
-  for (int c = 0; c < ns; ++c)
-    hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, (const float*)b->codes + (size_t)c * CODE,
-                       b->b0 + (size_t)c * HID, b->b4 + (size_t)c * HID);
-  const FwdKernel fwdk = fwd_kernel_for(D, query_fwd_variant());
-  const ErtArgs EX{nullptr, 1, 0.f, nullptr, nullptr};
-  const MaskArgs MX{nullptr, nullptr, nullptr, nullptr};
+  fold_codes(s, D, b->codes, ns, b->b0, b->b4);
   const int egrid = std::min(ctx->n_cu, ns * nt);
   if (sign) {
     DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)ns * np, s));
@@ -3180,18 +3123,14 @@ static int mesh_pass(dsr_mesher* m, int ns, float level, bool sign, const ErtArg
     E.refine = b->refine;
     E.audit = 0;
     E.diag = b->diag;
-    hipLaunchKernelGGL(lite_schedule().kernel, dim3(std::min(ctx->n_cu, ns * b->ntl)), dim3(512), 0, s, D,
-                       (const Tile*)b->ltiles, (const int*)b->cnt, (const ObjDesc*)b->desc, (const float4*)b->pts,
-                       (const float*)b->b0, (const float*)b->b4, b->lite, E);
+    launch_lite(s, std::min(ctx->n_cu, ns * b->ntl), D, {b->ltiles, b->cnt, b->desc, b->pts, b->b0, b->b4, b->lite, E});
     DSR_CHECK(ctx, hipEventRecord(b->ev[1], s));
     hipLaunchKernelGGL(k_mesh_mark, dim3((nt + 3) / 4, ns), dim3(256), 0, s, (const float*)b->lite,
                        (const unsigned char*)b->refine, d, n, np, nt, level, MESH_MARGIN, b->tflag, b->tmark, b->stat);
     mc_scan(s, b->tmark, ns * nt, b->tpos, b->bsum, b->cnt + 2);
     hipLaunchKernelGGL(k_mesh_compact, dim3((ns * nt + B - 1) / B), dim3(B), 0, s, (const int*)b->tmark,
                        (const int*)b->tpos, nt, n, ns * nt, b->etiles);
-    hipLaunchKernelGGL(fwdk, dim3(egrid), dim3(512), 0, s, D, (const Tile*)b->etiles, (const int*)(b->cnt + 2),
-                       (const ObjDesc*)b->desc, (const float4*)b->pts, (const float*)b->b0, (const float*)b->b4,
-                       b->vol, (unsigned*)nullptr, EX, MX);
+    launch_fwd(s, egrid, D, {b->etiles, b->cnt + 2, b->desc, b->pts, b->b0, b->b4, b->vol});
     hipLaunchKernelGGL(k_mesh_merge, dim3((n + 255) / 256, ns), dim3(256), 0, s, (const float*)b->lite,
                        (const unsigned char*)b->refine, (const unsigned char*)b->tflag, n, np, nt, level,
                        MESH_MARGIN, b->vol, b->slot_err, b->slot_viol);
@@ -3199,14 +3138,10 @@ static int mesh_pass(dsr_mesher* m, int ns, float level, bool sign, const ErtArg
                        (const int*)b->slot_viol, ns, nt, n, MESH_MARGIN, (const unsigned char*)b->tflag, b->rtiles,
                        b->cnt + 3, b->slot_redo, b->stat);
     // the rejected slots' remaining tiles (an empty table when the guard holds: the blocks return)
-    hipLaunchKernelGGL(fwdk, dim3(egrid), dim3(512), 0, s, D, (const Tile*)b->rtiles, (const int*)(b->cnt + 3),
-                       (const ObjDesc*)b->desc, (const float4*)b->pts, (const float*)b->b0, (const float*)b->b4,
-                       b->vol, (unsigned*)nullptr, EX, MX);
+    launch_fwd(s, egrid, D, {b->rtiles, b->cnt + 3, b->desc, b->pts, b->b0, b->b4, b->vol});
   } else {
     DSR_CHECK(ctx, hipEventRecord(b->ev[1], s));
-    hipLaunchKernelGGL(fwdk, dim3(egrid), dim3(512), 0, s, D, (const Tile*)b->atiles, (const int*)(b->cnt + 1),
-                       (const ObjDesc*)b->desc, (const float4*)b->pts, (const float*)b->b0, (const float*)b->b4,
-                       b->vol, (unsigned*)nullptr, EX, MX);
+    launch_fwd(s, egrid, D, {b->atiles, b->cnt + 1, b->desc, b->pts, b->b0, b->b4, b->vol});
   }
   DSR_CHECK(ctx, hipEventRecord(b->ev[2], s));
   hipLaunchKernelGGL(k_mcb_edges, dim3((n + B - 1) / B, ns), dim3(B), 0, s, (const float*)b->vol, d, np, level, b->flag);
@@ -3236,7 +3171,7 @@ int dsr_mesher_run_batch(dsr_mesher* m, int n_codes, const float* codes, float l
   st.margin = MESH_MARGIN;
   vert_off[0] = face_off[0] = 0;
   if (n_codes == 0) return 0;
-  if (!variant_kernels_ok(m->dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, m->dec)) return rc;
   hipSetDevice(ctx->device);
   const int cap = (int)std::max<size_t>(1, std::min<size_t>(MESH_MAX_SLOTS, MESH_BUDGET / mesh_slot_bytes(m)));
   int want = std::min(n_codes, cap);
@@ -3360,7 +3295,7 @@ struct dsr_renderer {
   dsr_camera cam{};
   int npix = 0, cap = 0;             // W*H; ray slots (2*W*H)
   int max_chunks = 0, max_tiles = 0; // of one pass
-  std::vector<void*> allocs;
+  DevArena mem;
   float *lam = nullptr, *lam0 = nullptr, *lam1 = nullptr, *dense = nullptr;
   int* state = nullptr;
   float4* cand = nullptr;            // cap + 64 * RENDER_PASS_OBJ (the normal pass pads tiles per object)
@@ -3380,20 +3315,6 @@ struct dsr_renderer {
   hipEvent_t ev[4] = {};
   dsr_render_stats st{};
 };
-
-static bool renderer_alloc(dsr_renderer* r, void** p, size_t bytes) {
-  if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  r->allocs.push_back(*p);
-  return true;
-}
-static void renderer_release(dsr_renderer* r, void* p) {
-  if (!p) return;
-  hipFree(p);
-  r->allocs.erase(std::remove(r->allocs.begin(), r->allocs.end(), p), r->allocs.end());
-}
 
 // One object's pose for the tracer: T_oc = inverse(t_cam_obj) in fp64, rounded once, the ball's
 // centre and radius (s = det(R_co)^(1/3)).  false: last row not 0 0 0 1, or det <= 0.
@@ -3475,7 +3396,6 @@ int dsr_renderer_destroy(dsr_renderer* r) {
   hipStreamSynchronize(r->ctx->stream);
   for (hipEvent_t e : r->ev)
     if (e) hipEventDestroy(e);
-  for (void* p : r->allocs) hipFree(p);
   delete r;
   return 0;
 }
@@ -3484,7 +3404,7 @@ int dsr_renderer_create(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_camera* 
   if (!ctx || !dec || !cam || !out) return fail(ctx, "null argument");
   *out = nullptr;
   if (const char* e = camera_error(cam)) return fail(ctx, e);
-  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, dec)) return rc;
   hipSetDevice(ctx->device);
   auto* r = new dsr_renderer();
   r->ctx = ctx;
@@ -3495,16 +3415,12 @@ int dsr_renderer_create(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_camera* 
   r->max_chunks = r->cap / RCHUNK + RENDER_PASS_OBJ;
   r->max_tiles = r->cap / TILE + RENDER_PASS_OBJ;
   const size_t cap = (size_t)r->cap;
-  auto A = [&](void** p, size_t bytes) { return renderer_alloc(r, p, bytes); };
-  bool ok = A((void**)&r->lam, sizeof(float) * cap) && A((void**)&r->lam0, sizeof(float) * cap) &&
-            A((void**)&r->lam1, sizeof(float) * cap) && A((void**)&r->dense, sizeof(float) * cap) &&
-            A((void**)&r->state, sizeof(int) * cap) &&
-            A((void**)&r->cand, sizeof(float4) * (cap + (size_t)TILE * RENDER_PASS_OBJ)) &&
-            A((void**)&r->ccnt, sizeof(int) * r->max_chunks) && A((void**)&r->gpos, sizeof(int) * r->max_chunks) &&
-            A((void**)&r->ntiles, sizeof(int)) && A((void**)&r->tiles, sizeof(Tile) * r->max_tiles) &&
-            A((void**)&r->keys, sizeof(unsigned long long) * r->npix) &&
-            A((void**)&r->depth, sizeof(float) * r->npix) && A((void**)&r->inst, sizeof(int) * r->npix) &&
-            A((void**)&r->ss, sizeof(RenderStepStats));
+  DevArena& M = r->mem;
+  bool ok = M.alloc(&r->lam, cap) && M.alloc(&r->lam0, cap) && M.alloc(&r->lam1, cap) && M.alloc(&r->dense, cap) &&
+            M.alloc(&r->state, cap) && M.alloc(&r->cand, cap + (size_t)TILE * RENDER_PASS_OBJ) &&
+            M.alloc(&r->ccnt, r->max_chunks) && M.alloc(&r->gpos, r->max_chunks) && M.alloc(&r->ntiles, 1) &&
+            M.alloc(&r->tiles, r->max_tiles) && M.alloc(&r->keys, r->npix) && M.alloc(&r->depth, r->npix) &&
+            M.alloc(&r->inst, r->npix) && M.alloc(&r->ss, 1);
   for (hipEvent_t& e : r->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -3519,13 +3435,6 @@ int dsr_renderer_stats_get(const dsr_renderer* r, dsr_render_stats* st) {
   if (!r || !st) return -2;
   *st = r->st;
   return 0;
-}
-
-// objects per pass: RENDER_PASS_OBJ, or DSR_RENDER_PASS_OBJ (1..64) under DSR_TEST_HOOKS=1
-static int render_pass_obj() {
-  const char* e = hook_env("DSR_RENDER_PASS_OBJ");
-  const int v = e ? atoi(e) : RENDER_PASS_OBJ;
-  return v >= 1 && v <= RENDER_PASS_OBJ ? v : RENDER_PASS_OBJ;
 }
 
 int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_obj, const dsr_render_object* in,
@@ -3546,7 +3455,7 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
   if (want_n && !normals) return fail(ctx, "null argument (normals requested)");
   for (int i = 0; i < n_obj; ++i)
     if (!in[i].code) return fail(ctx, "null argument (code)");
-  if (!variant_kernels_ok(r->dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, r->dec)) return rc;
   const dsr_decoder* dec = r->dec;
   const DevDecoder& D = dec->D;
   const RenderCam C{r->cam.fx, r->cam.fy, r->cam.cx, r->cam.cy, r->cam.width, r->cam.height};
@@ -3560,7 +3469,8 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
   std::vector<RayChunk> hc;
   struct Pass { int obj0, n_obj, chunk0, n_chunk, n_tiles_max; };
   std::vector<Pass> passes;
-  const int pass_obj = render_pass_obj();
+  // objects per pass: RENDER_PASS_OBJ, or DSR_RENDER_PASS_OBJ (1..64) under DSR_TEST_HOOKS=1
+  const int pass_obj = hook_int("DSR_RENDER_PASS_OBJ", RENDER_PASS_OBJ, 1, RENDER_PASS_OBJ);
   {
     Pass cur{0, 0, 0, 0, 0};
     int used = 0;
@@ -3610,35 +3520,33 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
     ~Drain() { (void)hipStreamSynchronize(s); }
   } drain{s};
   float* lnw = nullptr;          // LayerNorm decoders: the context stream's Jacobian workspace
-  if (want_n && D.ln_mask && !(lnw = ln_workspace(ctx, 0))) return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
+  if (int rc = decoder_ready(ctx, dec, want_n, &lnw)) return rc;
   // ---- per-call device arrays
   if (n_obj > r->obj_cap) {
     for (void* p : {(void*)r->objs, (void*)r->desc, (void*)r->codes, (void*)r->b0, (void*)r->b4, (void*)r->olive,
                     (void*)r->otile, (void*)r->counters})
-      renderer_release(r, p);
+      r->mem.release(p);
     r->objs = nullptr; r->desc = nullptr; r->codes = r->b0 = r->b4 = nullptr; r->olive = r->otile = r->counters = nullptr;
     r->obj_cap = 0;
     const size_t n = (size_t)std::max(n_obj, 16);
-    auto A = [&](void** p, size_t bytes) { return renderer_alloc(r, p, bytes); };
-    if (!A((void**)&r->objs, sizeof(RenderObj) * n) || !A((void**)&r->desc, sizeof(ObjDesc) * n) ||
-        !A((void**)&r->codes, sizeof(float) * CODE * n) || !A((void**)&r->b0, sizeof(float) * HID * n) ||
-        !A((void**)&r->b4, sizeof(float) * HID * n) || !A((void**)&r->olive, sizeof(int) * n) ||
-        !A((void**)&r->otile, sizeof(int) * n) || !A((void**)&r->counters, sizeof(int) * RC_INTS * n))
+    DevArena& M = r->mem;
+    if (!M.alloc(&r->objs, n) || !M.alloc(&r->desc, n) || !M.alloc(&r->codes, CODE * n) || !M.alloc(&r->b0, HID * n) ||
+        !M.alloc(&r->b4, HID * n) || !M.alloc(&r->olive, n) || !M.alloc(&r->otile, n) ||
+        !M.alloc(&r->counters, RC_INTS * n))
       return fail(ctx, "hipMalloc failed (render objects)");
     r->obj_cap = (int)n;
   }
   if (n_chunk > r->chunk_cap) {
-    renderer_release(r, r->chunks);
+    r->mem.release(r->chunks);
     r->chunks = nullptr;
     r->chunk_cap = 0;
     const size_t n = (size_t)std::max(n_chunk, 64);
-    if (!renderer_alloc(r, (void**)&r->chunks, sizeof(RayChunk) * n)) return fail(ctx, "hipMalloc failed (render chunks)");
+    if (!r->mem.alloc(&r->chunks, n)) return fail(ctx, "hipMalloc failed (render chunks)");
     r->chunk_cap = (int)n;
   }
   if (want_n && !r->raw) {
     const size_t np = (size_t)npix + (size_t)TILE * RENDER_PASS_OBJ;
-    if (!renderer_alloc(r, (void**)&r->normals, sizeof(float) * 3 * npix) ||
-        !renderer_alloc(r, (void**)&r->raw, sizeof(float) * (IN + 1) * np)) {
+    if (!r->mem.alloc(&r->normals, 3 * (size_t)npix) || !r->mem.alloc(&r->raw, (IN + 1) * np)) {
       r->raw = nullptr;
       return fail(ctx, "hipMalloc failed (render normals)");
     }
@@ -3652,15 +3560,10 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
     DSR_CHECK(ctx, hipMemsetAsync(r->counters, 0, sizeof(int) * RC_INTS * n_obj, s));
     if (n_chunk > 0)
       DSR_CHECK(ctx, hipMemcpyAsync(r->chunks, hc.data(), sizeof(RayChunk) * n_chunk, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < n_obj; ++i)
-      hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, (const float*)r->codes + (size_t)i * CODE,
-                         r->b0 + (size_t)i * HID, r->b4 + (size_t)i * HID);
+    fold_codes(s, D, r->codes, n_obj, r->b0, r->b4);
   }
   dsr_render_stats st{};
   st.n_obj = n_obj;
-  const FwdKernel fwdk = fwd_kernel_for(D, query_fwd_variant());
-  const ErtArgs EX{nullptr, 1, 0.f, nullptr, nullptr};
-  const MaskArgs MX{nullptr, nullptr, nullptr, nullptr};
   // ---- the march, pass by pass: everything enqueued, one synchronisation per pass
   for (const Pass& p : passes) {
     if (p.n_chunk == 0) continue;                       // only objects without rays
@@ -3678,9 +3581,7 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
       hipLaunchKernelGGL(k_rt_emit, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch, p.chunk0,
                          (const int*)r->gpos, (const int*)r->olive, (const int*)r->otile, (const int*)r->state,
                          (const float*)r->lam, r->cand, r->tiles, 0);
-      hipLaunchKernelGGL(fwdk, dim3(grid), dim3(512), 0, s, D, (const Tile*)r->tiles, (const int*)r->ntiles,
-                         (const ObjDesc*)r->desc, (const float4*)r->cand, (const float*)r->b0, (const float*)r->b4,
-                         r->dense, (unsigned*)nullptr, EX, MX);
+      launch_fwd(s, grid, D, {r->tiles, r->ntiles, r->desc, r->cand, r->b0, r->b4, r->dense});
       hipLaunchKernelGGL(k_rt_advance, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch,
                          (const float*)r->dense, r->lam, (const float*)r->lam0, (const float*)r->lam1, r->state,
                          r->keys, r->counters, r->ccnt, RenderMarch{hit_eps, damp, k == max_steps - 1});
@@ -3701,8 +3602,10 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
                        (const RayChunk*)r->chunks, (const int*)r->inst, r->counters);
   if (want_n) {
     DSR_CHECK(ctx, hipMemsetAsync(r->normals, 0, sizeof(float) * 3 * npix, s));
-    const JacKernel jack = jac_kernel_for(D);
-    GNParams GP{};
+    JacQuery jq{r->tiles, r->ntiles, r->desc, r->b0, r->b4};
+    jq.query_pts = r->cand;
+    jq.raw_out = r->raw;
+    jq.lnw = lnw;
     for (const Pass& p : passes) {
       if (p.n_chunk == 0) continue;
       const RayChunk* ch = r->chunks + p.chunk0;
@@ -3715,11 +3618,7 @@ int dsr_renderer_render(dsr_renderer* r, const dsr_render_params* params, int n_
       hipLaunchKernelGGL(k_rt_emit, dim3(p.n_chunk), dim3(RCHUNK), 0, s, C, (const RenderObj*)r->objs, ch, p.chunk0,
                          (const int*)r->gpos, (const int*)r->olive, (const int*)r->otile, (const int*)r->state,
                          (const float*)r->lam, r->cand, r->tiles, 1);
-      hipLaunchKernelGGL(jack, dim3(grid), dim3(512), 0, s, D, (const Tile*)r->tiles, (const int*)r->ntiles,
-                         (const ObjDesc*)r->desc, (const ObjState*)nullptr, (const float*)nullptr,
-                         (const float4*)nullptr, (const float*)nullptr, (const float*)r->b0, (const float*)r->b4, GP,
-                         (float*)nullptr, (const float4*)r->cand, r->raw, (float*)nullptr,
-                         MaskArgs{nullptr, nullptr, nullptr, nullptr}, lnw);
+      launch_jac(s, grid, D, jq);
       hipLaunchKernelGGL(k_rt_normals, dim3(grid), dim3(TILE), 0, s, C, (const RenderObj*)r->objs,
                          (const Tile*)r->tiles, (const int*)r->ntiles, (const float4*)r->cand, (const float*)r->raw,
                          r->normals);
@@ -3769,7 +3668,7 @@ struct dsr_scene {
   int max_obj = 0, max_pts = 0;
   size_t cap = 0;                    // pair slots: max(max_pts, SCENE_MIN_PAIRS)
   int max_chunks = 0, max_tiles = 0; // of one pass
-  std::vector<void*> allocs;
+  DevArena mem;
   // per object (max_obj)
   SceneObj* objs = nullptr;
   ObjDesc* desc = nullptr;
@@ -3799,15 +3698,6 @@ struct dsr_scene {
   std::vector<int> q_in;             // the last query's n_in
   dsr_scene_stats st{};
 };
-
-static bool scene_alloc(dsr_scene* sc, void** p, size_t bytes) {
-  if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  sc->allocs.push_back(*p);
-  return true;
-}
 
 // One object's pose for the query: T_ow = inverse(t_world_obj) in fp64 (adjugate / determinant, as
 // render_pose), rounded once; s = det(R)^(1/3) rounded once.  false: a non-finite entry, a last
@@ -3865,7 +3755,6 @@ int dsr_scene_destroy(dsr_scene* sc) {
   hipStreamSynchronize(sc->ctx->stream);
   for (hipEvent_t e : sc->ev)
     if (e) hipEventDestroy(e);
-  for (void* p : sc->allocs) hipFree(p);
   delete sc;
   return 0;
 }
@@ -3875,7 +3764,7 @@ int dsr_scene_create(dsr_ctx* ctx, const dsr_decoder* dec, int max_obj, int max_
   *out = nullptr;
   if (max_obj < 1) return fail(ctx, "max_obj must be >= 1");
   if (max_pts < 1 || max_pts > SCENE_MAX_PTS) return fail(ctx, "max_pts must be in [1, 2^24]");
-  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, dec)) return rc;
   hipSetDevice(ctx->device);
   auto* sc = new dsr_scene();
   sc->ctx = ctx;
@@ -3887,18 +3776,14 @@ int dsr_scene_create(dsr_ctx* ctx, const dsr_decoder* dec, int max_obj, int max_
   sc->max_tiles = (int)(sc->cap / TILE) + SCENE_PASS_OBJ;
   sc->hdesc.assign(max_obj, ObjDesc{});
   const size_t no = (size_t)max_obj, np = (size_t)max_pts, cap = sc->cap;
-  auto A = [&](void** p, size_t bytes) { return scene_alloc(sc, p, bytes); };
-  bool ok = A((void**)&sc->objs, sizeof(SceneObj) * no) && A((void**)&sc->desc, sizeof(ObjDesc) * no) &&
-            A((void**)&sc->codes, sizeof(float) * CODE * no) && A((void**)&sc->b0, sizeof(float) * HID * no) &&
-            A((void**)&sc->b4, sizeof(float) * HID * no) && A((void**)&sc->ocount, sizeof(int) * no) &&
-            A((void**)&sc->otile, sizeof(int) * no) && A((void**)&sc->wcount, sizeof(int) * no) &&
-            A((void**)&sc->wtile, sizeof(int) * no) && A((void**)&sc->nwin, sizeof(int) * no) &&
-            A((void**)&sc->sums, sizeof(SceneSums) * no) && A((void**)&sc->pts, sizeof(float) * 3 * np) &&
-            A((void**)&sc->keys, sizeof(unsigned long long) * np) && A((void**)&sc->dist, sizeof(float) * np) &&
-            A((void**)&sc->obj, sizeof(int) * np) && A((void**)&sc->cand, sizeof(float4) * cap) &&
-            A((void**)&sc->dense, sizeof(float) * cap) && A((void**)&sc->ccnt, sizeof(int) * sc->max_chunks) &&
-            A((void**)&sc->gpos, sizeof(int) * sc->max_chunks) && A((void**)&sc->ntiles, sizeof(int)) &&
-            A((void**)&sc->tiles, sizeof(Tile) * sc->max_tiles) && A((void**)&sc->part, sizeof(ScenePart) * sc->max_tiles);
+  DevArena& M = sc->mem;
+  bool ok = M.alloc(&sc->objs, no) && M.alloc(&sc->desc, no) && M.alloc(&sc->codes, CODE * no) &&
+            M.alloc(&sc->b0, HID * no) && M.alloc(&sc->b4, HID * no) && M.alloc(&sc->ocount, no) &&
+            M.alloc(&sc->otile, no) && M.alloc(&sc->wcount, no) && M.alloc(&sc->wtile, no) && M.alloc(&sc->nwin, no) &&
+            M.alloc(&sc->sums, no) && M.alloc(&sc->pts, 3 * np) && M.alloc(&sc->keys, np) && M.alloc(&sc->dist, np) &&
+            M.alloc(&sc->obj, np) && M.alloc(&sc->cand, cap) && M.alloc(&sc->dense, cap) &&
+            M.alloc(&sc->ccnt, sc->max_chunks) && M.alloc(&sc->gpos, sc->max_chunks) && M.alloc(&sc->ntiles, 1) &&
+            M.alloc(&sc->tiles, sc->max_tiles) && M.alloc(&sc->part, sc->max_tiles);
   for (hipEvent_t& e : sc->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -3932,7 +3817,7 @@ int dsr_scene_set_objects(dsr_scene* sc, int n_obj, const dsr_scene_object* in) 
       if (!std::isfinite(in[i].code[k])) return fail(ctx, "code must be finite (object " + std::to_string(i) + ")");
     std::memcpy(&hz[(size_t)i * CODE], in[i].code, sizeof(float) * dec->code_len);   // a 32-D code: zero-padded
   }
-  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, dec)) return rc;
   hipSetDevice(ctx->device);
   hipStream_t s = ctx->stream;
   sc->n_obj = -1;                    // (an error below leaves no half-uploaded map behind)
@@ -3940,22 +3825,13 @@ int dsr_scene_set_objects(dsr_scene* sc, int n_obj, const dsr_scene_object* in) 
   if (n_obj > 0) {
     DSR_CHECK(ctx, hipMemcpy(sc->objs, ho.data(), sizeof(SceneObj) * n_obj, hipMemcpyHostToDevice));
     DSR_CHECK(ctx, hipMemcpy(sc->codes, hz.data(), sizeof(float) * CODE * n_obj, hipMemcpyHostToDevice));
-    for (int i = 0; i < n_obj; ++i)
-      hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, dec->D, (const float*)sc->codes + (size_t)i * CODE,
-                         sc->b0 + (size_t)i * HID, sc->b4 + (size_t)i * HID);
+    fold_codes(s, dec->D, sc->codes, n_obj, sc->b0, sc->b4);
     DSR_CHECK(ctx, hipGetLastError());
     DSR_CHECK(ctx, hipStreamSynchronize(s));
   }
   sc->hobjs = std::move(ho);
   sc->n_obj = n_obj;
   return 0;
-}
-
-// objects per pass: SCENE_PASS_OBJ, or DSR_SCENE_PASS_OBJ (1..64) under DSR_TEST_HOOKS=1
-static int scene_pass_obj() {
-  const char* e = hook_env("DSR_SCENE_PASS_OBJ");
-  const int v = e ? atoi(e) : SCENE_PASS_OBJ;
-  return v >= 1 && v <= SCENE_PASS_OBJ ? v : SCENE_PASS_OBJ;
 }
 
 // The value pass of objects obj0 .. obj0 + k - 1 over the resident points, enqueued: bin, scan,
@@ -3976,10 +3852,7 @@ static int scene_value_pass(dsr_scene* sc, int obj0, int k, int n_pts, bool comp
                      (const float*)sc->pts, (const unsigned long long*)sc->keys, (const int*)sc->gpos,
                      (const int*)sc->ocount, (const int*)sc->otile, sc->cand, sc->tiles, 0);
   if (timing) DSR_CHECK(ctx, hipEventRecord(sc->ev[1], s));
-  hipLaunchKernelGGL(fwd_kernel_for(D, query_fwd_variant()), dim3(grid), dim3(512), 0, s, D, (const Tile*)sc->tiles,
-                     (const int*)sc->ntiles, (const ObjDesc*)sc->desc, (const float4*)sc->cand, (const float*)sc->b0,
-                     (const float*)sc->b4, sc->dense, (unsigned*)nullptr, ErtArgs{nullptr, 1, 0.f, nullptr, nullptr},
-                     MaskArgs{nullptr, nullptr, nullptr, nullptr});
+  launch_fwd(s, grid, D, {sc->tiles, sc->ntiles, sc->desc, sc->cand, sc->b0, sc->b4, sc->dense});
   if (timing) DSR_CHECK(ctx, hipEventRecord(sc->ev[2], s));
   if (composite) {
     hipLaunchKernelGGL(k_sc_min, dim3(grid), dim3(TILE), 0, s, (const SceneObj*)sc->objs, (const ObjDesc*)sc->desc,
@@ -4002,7 +3875,7 @@ int dsr_scene_query(dsr_scene* sc, int n_pts, const float* pts_world, float* dis
   if (n_pts < 0 || n_pts > sc->max_pts) return fail(ctx, "n_pts must be in [0, max_pts]");
   if (n_pts > 0 && (!pts_world || !dist || !obj)) return fail(ctx, "null argument");
   if (sc->n_obj < 0) return fail(ctx, "dsr_scene_query before dsr_scene_set_objects");
-  if (!variant_kernels_ok(sc->dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, sc->dec)) return rc;
   const int n_obj = sc->n_obj;
   const DevDecoder& D = sc->dec->D;
   dsr_scene_stats st{};
@@ -4028,18 +3901,19 @@ int dsr_scene_query(dsr_scene* sc, int n_pts, const float* pts_world, float* dis
   hipSetDevice(ctx->device);
   hipStream_t s = ctx->stream;
   float* lnw = nullptr;          // LayerNorm decoders: the context stream's Jacobian workspace
-  if (grad && D.ln_mask && !(lnw = ln_workspace(ctx, 0))) return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
+  if (int rc = decoder_ready(ctx, sc->dec, grad != nullptr, &lnw)) return rc;
   if (grad && !sc->raw) {
     const size_t np = (size_t)sc->max_pts + (size_t)TILE * SCENE_PASS_OBJ;
-    if (!scene_alloc(sc, (void**)&sc->grad, sizeof(float) * 3 * sc->max_pts) ||
-        !scene_alloc(sc, (void**)&sc->gcand, sizeof(float4) * np) ||
-        !scene_alloc(sc, (void**)&sc->raw, sizeof(float) * (IN + 1) * np)) {
+    if (!sc->mem.alloc(&sc->grad, 3 * (size_t)sc->max_pts) || !sc->mem.alloc(&sc->gcand, np) ||
+        !sc->mem.alloc(&sc->raw, (IN + 1) * np)) {
       sc->raw = nullptr;
       return fail(ctx, "hipMalloc failed (scene gradient)");
     }
   }
   // ---- passes: objects in input order, the largest k <= 64 with k * n_pts pairs in the buffers
-  const int k_pass = (int)std::min<size_t>((size_t)scene_pass_obj(), sc->cap / (size_t)n_pts);
+  // (SCENE_PASS_OBJ, or DSR_SCENE_PASS_OBJ (1..64) under DSR_TEST_HOOKS=1)
+  const size_t pass_obj = hook_int("DSR_SCENE_PASS_OBJ", SCENE_PASS_OBJ, 1, SCENE_PASS_OBJ);
+  const int k_pass = (int)std::min(pass_obj, sc->cap / (size_t)n_pts);
   for (int i = 0; i < n_obj; ++i) {
     sc->hdesc[i] = ObjDesc{};
     sc->hdesc[i].cand_off = (i % k_pass) * n_pts;
@@ -4065,6 +3939,10 @@ int dsr_scene_query(dsr_scene* sc, int n_pts, const float* pts_world, float* dis
                      sc->dist, sc->obj);
   if (grad) DSR_CHECK(ctx, hipMemsetAsync(sc->grad, 0, sizeof(float) * 3 * n_pts, s));
   DSR_CHECK(ctx, hipEventRecord(sc->ev[1], s));
+  JacQuery jq{sc->tiles, sc->ntiles, sc->desc, sc->b0, sc->b4};
+  jq.query_pts = sc->gcand;
+  jq.raw_out = sc->raw;
+  jq.lnw = lnw;
   for (int o0 = 0; o0 < n_obj; o0 += k_pass) {
     const int k = std::min(k_pass, n_obj - o0);
     hipLaunchKernelGGL(k_sc_winners, dim3(k * nc), dim3(SCHUNK), 0, s, o0, nc, n_pts, (const unsigned long long*)sc->keys,
@@ -4076,11 +3954,7 @@ int dsr_scene_query(dsr_scene* sc, int n_pts, const float* pts_world, float* dis
     hipLaunchKernelGGL(k_sc_emit, dim3(k * nc), dim3(SCHUNK), 0, s, o0, nc, n_pts, (const SceneObj*)sc->objs,
                        (const float*)sc->pts, (const unsigned long long*)sc->keys, (const int*)sc->gpos,
                        (const int*)sc->wcount, (const int*)sc->wtile, sc->gcand, sc->tiles, 1);
-    hipLaunchKernelGGL(jac_kernel_for(D), dim3(grid), dim3(512), 0, s, D, (const Tile*)sc->tiles, (const int*)sc->ntiles,
-                       (const ObjDesc*)sc->desc, (const ObjState*)nullptr, (const float*)nullptr,
-                       (const float4*)nullptr, (const float*)nullptr, (const float*)sc->b0, (const float*)sc->b4,
-                       GNParams{}, (float*)nullptr, (const float4*)sc->gcand, sc->raw, (float*)nullptr,
-                       MaskArgs{nullptr, nullptr, nullptr, nullptr}, lnw);
+    launch_jac(s, grid, D, jq);
     hipLaunchKernelGGL(k_sc_grad, dim3(grid), dim3(TILE), 0, s, (const SceneObj*)sc->objs, (const Tile*)sc->tiles,
                        (const int*)sc->ntiles, (const float4*)sc->gcand, (const float*)sc->raw, sc->grad);
   }
@@ -4149,12 +4023,12 @@ int dsr_scene_peek(dsr_scene* sc, int obj, int cap, int* idx, float* x_obj, floa
 int dsr_sdf_eval(dsr_ctx* ctx, const dsr_decoder* dec, const float* code, const float* pts, int n,
                  float* sdf, float* jac) {
   if (!ctx || !dec || !code || (n > 0 && (!pts || !sdf))) return fail(ctx, "null argument");
-  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
+  if (int rc = decoder_ready(ctx, dec)) return rc;
   if (n <= 0) return 0;
   hipSetDevice(ctx->device);
   hipStream_t s = ctx->stream;
   float* lnw = nullptr;          // LayerNorm decoders: the context stream's Jacobian workspace
-  if (jac && dec->D.ln_mask && !(lnw = ln_workspace(ctx, 0))) return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
+  if (int rc = decoder_ready(ctx, dec, jac != nullptr, &lnw)) return rc;
   float zc[CODE] = {};                               // a 32-D code runs padded with zeros
   std::memcpy(zc, code, sizeof(float) * dec->code_len);
   const int nt = (n + TILE - 1) / TILE;
@@ -4168,52 +4042,39 @@ int dsr_sdf_eval(dsr_ctx* ctx, const dsr_decoder* dec, const float* code, const 
   for (int t = 0; t < nt; ++t) ht[t] = Tile{0, jac ? 2 : 0, t * TILE, std::min(TILE, n - t * TILE)};
   ObjDesc d{};
   d.n_pts = n;
-  void *dp = nullptr, *dz = nullptr, *db0 = nullptr, *db4 = nullptr, *dt = nullptr, *dnt = nullptr,
-       *dout = nullptr, *dd = nullptr;
-  std::vector<void*> al;
-  auto A = [&](void** p, size_t bytes) {
-    if (hipMalloc(p, bytes) != hipSuccess) return false;
-    al.push_back(*p);
-    return true;
-  };
-  auto cleanup = [&]() { for (void* p : al) hipFree(p); };
+  float4* dp = nullptr;
+  float *dz = nullptr, *db0 = nullptr, *db4 = nullptr, *dout = nullptr;
+  Tile* dt = nullptr;
+  int* dnt = nullptr;
+  ObjDesc* dd = nullptr;
+  DevArena mem;                                      // (freed on return: after the copy back)
   const size_t outw = jac ? (size_t)(IN + 1) : 1;
-  if (!A(&dp, sizeof(float4) * hp.size()) || !A(&dz, sizeof(float) * CODE) || !A(&db0, sizeof(float) * HID) ||
-      !A(&db4, sizeof(float) * HID) || !A(&dt, sizeof(Tile) * nt) || !A(&dnt, sizeof(int)) ||
-      !A(&dout, sizeof(float) * outw * nt * TILE) || !A(&dd, sizeof(ObjDesc))) {
-    cleanup();
+  if (!mem.alloc(&dp, hp.size()) || !mem.alloc(&dz, CODE) || !mem.alloc(&db0, HID) || !mem.alloc(&db4, HID) ||
+      !mem.alloc(&dt, nt) || !mem.alloc(&dnt, 1) || !mem.alloc(&dout, outw * nt * TILE) || !mem.alloc(&dd, 1))
     return fail(ctx, "hipMalloc failed (sdf_eval)");
-  }
   bool ok = hipMemcpy(dp, hp.data(), sizeof(float4) * hp.size(), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(dz, zc, sizeof(float) * CODE, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(dt, ht.data(), sizeof(Tile) * nt, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(dnt, &nt, sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(dd, &d, sizeof(ObjDesc), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { cleanup(); return fail(ctx, "hipMemcpy failed (sdf_eval)"); }
+  if (!ok) return fail(ctx, "hipMemcpy failed (sdf_eval)");
   const DevDecoder& D = dec->D;
-  hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, (const float*)dz, (float*)db0, (float*)db4);
+  fold_codes(s, D, dz, 1, db0, db4);
   const int grid = std::min(ctx->n_cu, nt);
   if (jac) {
-    GNParams P{};
-    hipLaunchKernelGGL(jac_kernel_for(D), dim3(grid), dim3(512), 0, s, D, (const Tile*)dt, (const int*)dnt,
-                       (const ObjDesc*)dd, (const ObjState*)nullptr, (const float*)nullptr,
-                       (const float4*)nullptr, (const float*)nullptr, (const float*)db0, (const float*)db4, P,
-                       (float*)nullptr, (const float4*)dp, (float*)dout, (float*)nullptr,
-                       MaskArgs{nullptr, nullptr, nullptr, nullptr}, lnw);
+    JacQuery q{dt, dnt, dd, db0, db4};
+    q.query_pts = dp;
+    q.raw_out = dout;
+    q.lnw = lnw;
+    launch_jac(s, grid, D, q);
   } else {
-    hipLaunchKernelGGL(fwd_kernel_for(D, query_fwd_variant()), dim3(grid), dim3(512), 0, s, D, (const Tile*)dt, (const int*)dnt,
-                       (const ObjDesc*)dd, (const float4*)dp, (const float*)db0, (const float*)db4, (float*)dout,
-                       (unsigned*)nullptr, ErtArgs{nullptr, 1, 0.f, nullptr, nullptr},
-                       MaskArgs{nullptr, nullptr, nullptr, nullptr});
+    launch_fwd(s, grid, D, {dt, dnt, dd, dp, db0, db4, dout});
   }
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-    cleanup();
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
     return fail(ctx, "kernel failed (sdf_eval)");
-  }
   std::vector<float> h(outw * n);
-  ok = hipMemcpy(h.data(), dout, sizeof(float) * h.size(), hipMemcpyDeviceToHost) == hipSuccess;
-  cleanup();
-  if (!ok) return fail(ctx, "hipMemcpy D2H failed (sdf_eval)");
+  if (hipMemcpy(h.data(), dout, sizeof(float) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ctx, "hipMemcpy D2H failed (sdf_eval)");
   // jac rows: [code (code_len) | xyz (3)] (the kernels' 64-D layout holds code 0..63, xyz 64..66)
   const int L = dec->code_len, jw = L + 3;
   for (int i = 0; i < n; ++i) {
@@ -4236,9 +4097,8 @@ int dsr_pose_only_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_pa
   if (!ctx || !dec || !p || !t_out || (n_obj > 0 && !in)) return fail(ctx, "null argument");
   if (n_obj <= 0) return fail(ctx, "n_obj must be > 0");
   if (p->code_len != dec->code_len) return fail(ctx, "optimizer code_len != decoder code_len");
-  if (!variant_kernels_ok(dec)) return fail(ctx, "use_tanh / xyz_in_all / LayerNorm decoders run on the split-fp16 kernels only");
   float* lnw = nullptr;          // LayerNorm decoders: the context stream's Jacobian workspace
-  if (dec->D.ln_mask && !(lnw = ln_workspace(ctx, 0))) return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
+  if (int rc = decoder_ready(ctx, dec, true, &lnw)) return rc;
   for (int o = 0; o < n_obj; ++o) {
     if (!in[o].code || (in[o].n_pts > 0 && !in[o].pts)) return fail(ctx, "null argument");
     if (in[o].n_pts < 0) return fail(ctx, "bad surface points");
@@ -4259,39 +4119,30 @@ int dsr_pose_only_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_pa
     cap_tiles += (x.n_pts + TILE - 1) / TILE;
   }
   const int iters = p->pose_only_iterations;
-  void *dpts = nullptr, *dst = nullptr, *dz = nullptr, *db0 = nullptr, *db4 = nullptr, *dt = nullptr,
-       *dnt = nullptr, *dslots = nullptr, *ddesc = nullptr, *dtin = nullptr, *doc = nullptr, *dzb = nullptr,
-       *dres = nullptr, *dout = nullptr;
-  std::vector<void*> al;
-  auto A = [&](void** q, size_t bytes) {
-    if (hipMalloc(q, std::max<size_t>(bytes, 256)) != hipSuccess) return false;
-    al.push_back(*q);
-    return true;
-  };
-  auto cleanup = [&]() { for (void* q : al) hipFree(q); };
+  float *dpts = nullptr, *dz = nullptr, *db0 = nullptr, *db4 = nullptr, *dslots = nullptr, *dtin = nullptr,
+        *dzb = nullptr, *dres = nullptr, *dout = nullptr;
+  ObjState* dst = nullptr;
+  ObjDesc* ddesc = nullptr;
+  Tile* dt = nullptr;
+  int *dnt = nullptr, *doc = nullptr;
+  DevArena mem;                                      // (freed on return: after the copy back)
   const size_t n = (size_t)n_obj;
-  if (!A(&dpts, sizeof(float) * 3 * cap_pts) || !A(&dst, sizeof(ObjState) * n) ||
-      !A(&dz, sizeof(float) * CODE * n) || !A(&db0, sizeof(float) * HID * n) || !A(&db4, sizeof(float) * HID * n) ||
-      !A(&dt, sizeof(Tile) * cap_tiles) || !A(&dnt, sizeof(int)) ||
-      !A(&dslots, sizeof(float) * SLOT_FLOATS * cap_tiles) || !A(&ddesc, sizeof(ObjDesc) * n) ||
-      !A(&dtin, sizeof(float) * 16 * n) || !A(&doc, sizeof(int) * n) || !A(&dzb, sizeof(float) * CODE * n) ||
-      !A(&dres, sizeof(float) * cap_pts) || !A(&dout, sizeof(float) * 16 * n)) {
-    cleanup();
+  if (!mem.alloc(&dpts, 3 * cap_pts) || !mem.alloc(&dst, n) || !mem.alloc(&dz, CODE * n) || !mem.alloc(&db0, HID * n) ||
+      !mem.alloc(&db4, HID * n) || !mem.alloc(&dt, cap_tiles) || !mem.alloc(&dnt, 1) ||
+      !mem.alloc(&dslots, SLOT_FLOATS * cap_tiles) || !mem.alloc(&ddesc, n) || !mem.alloc(&dtin, 16 * n) ||
+      !mem.alloc(&doc, n) || !mem.alloc(&dzb, CODE * n) || !mem.alloc(&dres, cap_pts) || !mem.alloc(&dout, 16 * n))
     return fail(ctx, "hipMalloc failed (pose_only)");
-  }
   const std::vector<int> zeros(n, 0);
   bool ok = hipMemcpy(dz, hz.data(), sizeof(float) * CODE * n, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(dtin, t_in.data(), sizeof(float) * 16 * n, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(doc, zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { cleanup(); return fail(ctx, "hipMemcpy failed (pose_only)"); }
+  if (!ok) return fail(ctx, "hipMemcpy failed (pose_only)");
   const DevDecoder& D = dec->D;
   GNParams P = make_params(p, false);
   P.raw_residual = 1;
-  for (int o = 0; o < n_obj; ++o)
-    hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, (const float*)dz + (size_t)CODE * o,
-                       (float*)db0 + (size_t)HID * o, (float*)db4 + (size_t)HID * o);
+  fold_codes(s, D, dz, n_obj, db0, db4);
   hipLaunchKernelGGL(k_init_state, dim3(n_obj), dim3(64), 0, s, n_obj, (const float*)dtin, (const int*)doc,
-                     (const float*)dz, (ObjState*)dst, (float*)dzb, 1);               // :57 t_obj_cam = inv
+                     (const float*)dz, dst, dzb, 1);                                   // :57 t_obj_cam = inv
   int n_tiles = 0;
   // points, descriptors and tile table of the current point sets (objects back to back)
   auto upload = [&]() {
@@ -4315,30 +4166,28 @@ int dsr_pose_only_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_pa
            (ht.empty() || hipMemcpy(dt, ht.data(), sizeof(Tile) * ht.size(), hipMemcpyHostToDevice) == hipSuccess) &&
            hipMemcpy(dnt, &n_tiles, sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
   };
-  if (!upload()) { cleanup(); return fail(ctx, "hipMemcpy failed (pose_only tiles)"); }
+  if (!upload()) return fail(ctx, "hipMemcpy failed (pose_only tiles)");
   std::vector<char> emptied(n, 0);
   for (int o = 0; o < n_obj; ++o)           // no points: J^T J / 0 -> a NaN pose (golden F10)
     if (in[o].n_pts == 0) emptied[o] = 1;
+  JacQuery jq{dt, dnt, ddesc, db0, db4};
+  jq.st = dst;
+  jq.surf_pts = dpts;
+  jq.P = P;
+  jq.slots = dslots;
+  jq.lnw = lnw;
   for (int e = 0; e < iters; ++e) {
     const bool filter = (e == 4) && (e + 1 < iters);   // :77-79 inlier filter (effective only past 5 iters)
-    if (n_tiles > 0)
-      hipLaunchKernelGGL(jac_kernel_for(D), dim3(std::max(1, std::min(ctx->n_cu, n_tiles))), dim3(512), 0, s, D,
-                         (const Tile*)dt, (const int*)dnt, (const ObjDesc*)ddesc, (const ObjState*)dst,
-                         (const float*)dpts, (const float4*)nullptr, (const float*)nullptr, (const float*)db0,
-                         (const float*)db4, P, (float*)dslots, (const float4*)nullptr, (float*)nullptr,
-                         filter ? (float*)dres : (float*)nullptr, MaskArgs{nullptr, nullptr, nullptr, nullptr},
-                         lnw);
-    hipLaunchKernelGGL(k_solve_pose, dim3(n_obj), dim3(256), 0, s, (const ObjDesc*)ddesc, (ObjState*)dst,
-                       (const float*)dslots);
+    jq.res_out = filter ? dres : nullptr;
+    if (n_tiles > 0) launch_jac(s, std::max(1, std::min(ctx->n_cu, n_tiles)), D, jq);
+    hipLaunchKernelGGL(k_solve_pose, dim3(n_obj), dim3(256), 0, s, (const ObjDesc*)ddesc, dst, (const float*)dslots);
     if (filter) {
       size_t tot = 0;
       for (int o = 0; o < n_obj; ++o) tot += hp[o].size() / 3;
       std::vector<float> res(std::max<size_t>(1, tot));
       if (hipStreamSynchronize(s) != hipSuccess ||      // ctx->stream is non-blocking
-          (tot && hipMemcpy(res.data(), dres, sizeof(float) * tot, hipMemcpyDeviceToHost) != hipSuccess)) {
-        cleanup();
+          (tot && hipMemcpy(res.data(), dres, sizeof(float) * tot, hipMemcpyDeviceToHost) != hipSuccess))
         return fail(ctx, "hipMemcpy failed (pose_only residuals)");
-      }
       size_t off = 0;
       for (int o = 0; o < n_obj; ++o) {
         const size_t np = hp[o].size() / 3;
@@ -4349,15 +4198,13 @@ int dsr_pose_only_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_pa
         hp[o].swap(kept);
         if (hp[o].empty()) emptied[o] = 1;    // the reference goes on with an empty set: NaN pose
       }
-      if (!upload()) { cleanup(); return fail(ctx, "hipMemcpy failed (pose_only filter)"); }
+      if (!upload()) return fail(ctx, "hipMemcpy failed (pose_only filter)");
     }
   }
-  hipLaunchKernelGGL(k_inv_out, dim3((n_obj + 63) / 64), dim3(64), 0, s, n_obj, (const ObjState*)dst,
-                     (float*)dout);                                                    // :84
+  hipLaunchKernelGGL(k_inv_out, dim3((n_obj + 63) / 64), dim3(64), 0, s, n_obj, (const ObjState*)dst, dout);   // :84
   std::vector<float> T((size_t)16 * n);
   ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
        hipMemcpy(T.data(), dout, sizeof(float) * 16 * n, hipMemcpyDeviceToHost) == hipSuccess;
-  cleanup();
   if (!ok) return fail(ctx, "pose_only failed");
   for (int o = 0; o < n_obj; ++o) {
     float* to = t_out + 16 * o;
