@@ -14,6 +14,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -97,6 +98,19 @@ static int split_ring() {
   const int r = e ? atoi(e) : DSR_DEFAULT_SPLIT_RING;
   return (r >= 2 && r <= 4) ? r : 0;
 }
+
+static int fwd_variant() {
+  const char* e = hook_env("DSR_FWD_VARIANT");
+  return e ? atoi(e) : DSR_DEFAULT_FWD_VARIANT;
+}
+static int jac_variant() {
+  const char* e = hook_env("DSR_JAC_VARIANT");
+  return e ? atoi(e) : 12;
+}
+// the forward variant of a one-launch decoder query (dsr_sdf_eval, the mesher): the XCD soft-sync
+// variants (bit 0) need the per-batch sync counter these launches have not got, so their bit 0 is
+// dropped there (the same kernels otherwise)
+static int query_fwd_variant() { return fwd_variant() & ~1; }
 using FwdKernel = void (*)(DevDecoder, const Tile*, const int*, const ObjDesc*, const float4*, const float*,
                            const float*, float*, unsigned*, ErtArgs, MaskArgs);
 // split-fp16 forward with X's mask bit (512) and the ring depth in bits 10-11
@@ -109,45 +123,70 @@ static FwdKernel fwd16_kernel() {
   }
   return k_mlp_fwd16<true, MSK>;
 }
-static FwdKernel fwd_kernel(int v) {
-  switch (v & 15) {
-    case 1: return k_mlp_fwd<1>;
-    case 2: return k_mlp_fwd<2>;
-    case 3: return k_mlp_fwd<3>;
-    case 6: return k_mlp_fwd<6>;
-    case 7: return k_mlp_fwd<7>;
-    case 8: return k_mlp_fwd16<false, 0>;
-    case 12: return fwd16_kernel<0>();
-    default: return k_mlp_fwd<0>;
-  }
+// What a kernel family runs and what dsr_stats reports of it: the variant number, the kernel, and
+// the A-ring depth of the split kernels
+struct FwdChoice {
+  int number;
+  FwdKernel kernel;
+  int ring;
+};
+// the low nibble of v selects: a table row, or 12, the split kernels at fwd16_kernel's ring depth;
+// an unknown one runs k_mlp_fwd<0> and reports v without it
+static FwdChoice fwd_kernel(int v) {
+  static const struct {
+    int number;
+    FwdKernel kernel;
+  } table[] = {{1, k_mlp_fwd<1>}, {2, k_mlp_fwd<2>}, {3, k_mlp_fwd<3>},
+               {6, k_mlp_fwd<6>}, {7, k_mlp_fwd<7>}, {8, k_mlp_fwd16<false, 0>}};
+  const int ring = split_ring();
+  for (const auto& c : table)
+    if (c.number == (v & 15)) return {v, c.kernel, ring};
+  if ((v & 15) == 12) return {v, fwd16_kernel<0>(), ring};
+  return {v & ~15, k_mlp_fwd<0>, ring};
 }
 using JacKernel = void (*)(DevDecoder, const Tile*, const int*, const ObjDesc*, const ObjState*, const float*,
                            const float4*, const float*, const float*, const float*, GNParams, float*,
                            const float4*, float*, float*, MaskArgs, float*);
-static int jac_variant();
-static JacKernel jac_kernel() {
-  const int v = jac_variant();
-  switch (v) {
-    case 8: return k_mlp_jac16<false, 0>;
-    case 12:
-      switch (split_ring()) {
-        case 2: return k_mlp_jac16<true, 2>;
-        case 3: return k_mlp_jac16<true, 3>;
-        case 4: return k_mlp_jac16<true, 4>;
-      }
-      return k_mlp_jac16<true, 0>;
-  }
-  return k_mlp_jac;
+struct JacChoice {
+  int number;
+  JacKernel kernel;
+  int ring = -1;            // (a table row's ring -1: the row holds for any depth)
+};
+// an unknown DSR_JAC_VARIANT runs k_mlp_jac and reports 0
+static JacChoice jac_kernel() {
+  static const JacChoice table[] = {{8, k_mlp_jac16<false, 0>},
+                                    {12, k_mlp_jac16<true, 2>, 2},
+                                    {12, k_mlp_jac16<true, 3>, 3},
+                                    {12, k_mlp_jac16<true, 4>, 4},
+                                    {12, k_mlp_jac16<true, 0>, 0}};
+  const int v = jac_variant(), ring = split_ring();
+  for (const JacChoice& c : table)
+    if (c.number == v && (c.ring < 0 || c.ring == ring)) return {v, c.kernel, ring};
+  return {0, k_mlp_jac, ring};
 }
+struct dsr_decoder {
+  dsr_ctx* ctx = nullptr;
+  float* dmem = nullptr;
+  size_t bytes = 0;
+  DevDecoder D{};
+  int code_len = 64;
+  dsr_decoder_info info{};      // load-time lite qualification (decoder_qualify)
+};
+
 // Decoder variants (use_tanh / xyz_in_all / LayerNorm) run their own instantiations of the
 // split-fp16 kernels (ring depth 2), so the shipped topology's kernels carry none of their code;
 // variant_kernels_ok has already refused the fp32-MFMA A/B variants for them
 static bool is_variant(const DevDecoder& D) { return D.xyz_all || D.use_tanh || D.ln_mask; }
-static FwdKernel fwd_kernel_for(const DevDecoder& D, int v) {
-  return is_variant(D) ? k_mlp_fwd16<true, 1024 | 8192> : fwd_kernel(v);
+// the decoder variants (use_tanh, xyz_in_all) are implemented in the split-fp16 kernels only
+// (the fp32-MFMA A/B variants k_mlp_fwd / k_mlp_jac implement the shipped topology)
+static bool variant_kernels_ok(const dsr_decoder* dec) {
+  return !is_variant(dec->D) || (fwd_variant() == 12 && jac_variant() == 12);
 }
-static JacKernel jac_kernel_for(const DevDecoder& D) {
-  return is_variant(D) ? k_mlp_jac16<true, 2, true> : jac_kernel();
+static FwdChoice fwd_kernel_for(const DevDecoder& D, int v) {
+  return is_variant(D) ? FwdChoice{12, k_mlp_fwd16<true, 1024 | 8192>, 2} : fwd_kernel(v);
+}
+static JacChoice jac_kernel_for(const DevDecoder& D) {
+  return is_variant(D) ? JacChoice{12, k_mlp_jac16<true, 2, true>, 2} : jac_kernel();
 }
 // Lite-pass schedule (DSR_LITE_VARIANT; dsr_mlp_lite.hpp: k_mlp_fwd_lite_st<SWZ, PIN>).  The
 // numbers are names (environment, dsr_stats.lite_variant); all three give bitwise equal values:
@@ -193,28 +232,6 @@ static int lite_lag(bool hooks) {
   const int v = e ? atoi(e) : 4;
   return v < 0 ? 0 : (v > 7 ? 7 : v);
 }
-static int fwd_variant() {
-  const char* e = hook_env("DSR_FWD_VARIANT");
-  return e ? atoi(e) : DSR_DEFAULT_FWD_VARIANT;
-}
-// the forward variant of a one-launch decoder query (dsr_sdf_eval, the mesher): the XCD soft-sync
-// variants (bit 0) need the per-batch sync counter these launches have not got, so their bit 0 is
-// dropped there (the same kernels otherwise)
-static int query_fwd_variant() { return fwd_variant() & ~1; }
-static int jac_variant();
-// the decoder variants (use_tanh, xyz_in_all) are implemented in the split-fp16 kernels only
-// (the fp32-MFMA A/B variants k_mlp_fwd / k_mlp_jac implement the shipped topology)
-#define variant_kernels_ok(dec) \
-  (!((dec)->D.xyz_all || (dec)->D.use_tanh || (dec)->D.ln_mask) || (fwd_variant() == 12 && jac_variant() == 12))
-
-struct dsr_decoder {
-  dsr_ctx* ctx = nullptr;
-  float* dmem = nullptr;
-  size_t bytes = 0;
-  DevDecoder D{};
-  int code_len = 64;
-  dsr_decoder_info info{};      // load-time lite qualification (decoder_qualify)
-};
 
 struct DevBuf {
   void* p = nullptr;
@@ -539,8 +556,6 @@ static int pack_frag16(std::vector<_Float16>& out, int rows_pad, int cols_pad,
   return sw;
 }
 
-static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec);
-
 // The split GEMMs' inputs at a fixed probe set — 256 points uniform in the unit ball (fixed LCG),
 // code 0 — in the packed column order pack_frag16 uses, for its feedback rounding:
 //  fwd[l], l = 1..7: lin l's input h_{l-1} (with xyz at 509..511 under xyz_in_all); lin4's columns
@@ -677,6 +692,165 @@ static DecoderProbe decoder_probe(const int* od, const int* id, const std::vecto
   return pr;
 }
 
+// a code's bias folds of lin0 and lin4: bias + W_z z, per code (every decoder query runs on them)
+__global__ void k_fold_code(DevDecoder D, const float* __restrict__ z, float* __restrict__ bias0f,
+                            float* __restrict__ bias4f) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= HID) return;
+  float s0 = 0.f, s4 = 0.f;
+  for (int k = 0; k < CODE; ++k) {
+    s0 = __builtin_fmaf(D.W0z[k * HID + n], z[k], s0);
+    s4 = __builtin_fmaf(D.W4z[k * HID + n], z[k], s4);
+  }
+  bias0f[n] = D.bias[0][n] + s0;
+  bias4f[n] = D.bias[4][n] + s4;
+}
+// the bias folds of n codes (64 floats each, back to back) into b0 / b4 (HID floats each)
+static void fold_codes(hipStream_t s, const DevDecoder& D, const float* codes, int n, float* b0, float* b4) {
+  for (int i = 0; i < n; ++i)
+    hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, codes + (size_t)i * CODE, b0 + (size_t)i * HID,
+                       b4 + (size_t)i * HID);
+}
+
+// ------------------------------------------------------------------------------------
+// load-time qualification of the lite pass (include/dsr.h: dsr_decoder_info)
+// ------------------------------------------------------------------------------------
+// The lite pass classifies ray samples with one fp16 product; the per-object margin and the
+// audit (DESIGN.md §3.4) guard it at run time, but their evidence is empirical: a decoder with
+// larger weights or activations has larger fp16 errors.  So before any batch trusts the lite
+// pass with a loaded decoder, the decoder decodes a fixed probe set through both passes — the
+// same kernels, tiles and bias fold a batch uses — and the lite error is measured against the
+// distance of each exact value to its nearest class boundary (full <= -th < band < th <=
+// empty, th = 0.01, loss_utils.py:40-48, loss.py:98-102), floored at the margin floor 0.002, and
+// against the floor itself near the surface (|exact| < 0.1, where the band and the audit shell
+// lie).  Above half of either anywhere, the decoder is lite-ineligible and every batch decodes
+// exactly.
+static constexpr int PROBE_POINTS = 65536, PROBE_CODES = 4;
+static constexpr float PROBE_TH = 0.01f, PROBE_FLOOR = 0.002f, PROBE_MAX_RATIO = 0.5f;
+
+static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (dec->D.xyz_all || dec->D.use_tanh || dec->D.ln_mask) {   // the lite kernels: the shipped topology only
+    dsr_decoder_info& I = dec->info;
+    I.code_len = dec->code_len;
+    I.lite_eligible = 0;
+    I.lite_probe_ratio = I.lite_probe_max_err = I.lite_probe_max_err_all = NAN;
+    I.probe_points = I.probe_codes = 0;
+    I.probe_ms = 0.0;
+    return 0;
+  }
+  const int n = PROBE_POINTS, nc = PROBE_CODES, tot = n * nc;
+  uint64_t s = 0x9E3779B97F4A7C15ull;           // fixed LCG: the probe set is part of the contract
+  auto u01 = [&]() {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return (double)(s >> 11) * (1.0 / 9007199254740992.0);
+  };
+  std::vector<float4> cand(tot);
+  for (int i = 0; i < n;) {                     // uniform in the unit ball (rejection from the cube)
+    const double x = 2 * u01() - 1, y = 2 * u01() - 1, z = 2 * u01() - 1;
+    if (x * x + y * y + z * z >= 1.0) continue;
+    for (int c = 0; c < nc; ++c) {
+      int idx = i;
+      float fi;
+      std::memcpy(&fi, &idx, sizeof(float));
+      cand[(size_t)c * n + i] = make_float4((float)x, (float)y, (float)z, fi);
+    }
+    ++i;
+  }
+  static const float scale[PROBE_CODES] = {0.0f, 0.1f, 0.3f, 1.0f};
+  std::vector<float> hz((size_t)nc * CODE);
+  for (int c = 0; c < nc; ++c)
+    for (int k = 0; k < CODE; ++k) {               // Box-Muller
+      const double r = std::sqrt(-2.0 * std::log(1.0 - u01())), t = 2.0 * M_PI * u01();
+      hz[(size_t)c * CODE + k] = (float)(scale[c] * r * std::cos(t));
+    }
+  std::vector<ObjDesc> hd(nc);
+  std::vector<ObjState> hs(nc);
+  std::vector<Tile> tl, te;
+  for (int c = 0; c < nc; ++c) {
+    hd[c] = ObjDesc{};
+    hd[c].ray_off = c * n;
+    hd[c].n_rays = n;
+    hd[c].cand_off = c * n;
+    std::memset(&hs[c], 0, sizeof(ObjState));    // lite_margin 0: flags are not used here
+    for (int t = 0; t * LTILE < n; ++t) tl.push_back(Tile{c, 0, t * LTILE, std::min(LTILE, n - t * LTILE)});
+    for (int t = 0; t * TILE < n; ++t) te.push_back(Tile{c, 0, t * TILE, std::min(TILE, n - t * TILE)});
+  }
+  const int ntl = (int)tl.size(), nte = (int)te.size();
+  DevArena mem;
+  float4* dc = nullptr;
+  float *dl = nullptr, *de = nullptr, *dz = nullptr, *db0 = nullptr, *db4 = nullptr;
+  unsigned char* dref = nullptr;
+  int *ddead = nullptr, *dntl = nullptr, *dnte = nullptr;
+  ObjDesc* ddesc = nullptr;
+  ObjState* dst = nullptr;
+  Tile *dtl = nullptr, *dte = nullptr;
+  if (!mem.alloc(&dc, tot) || !mem.alloc(&dl, tot) || !mem.alloc(&de, tot) || !mem.alloc(&dz, hz.size()) ||
+      !mem.alloc(&db0, HID * nc) || !mem.alloc(&db4, HID * nc) || !mem.alloc(&dref, tot) ||
+      !mem.alloc(&ddead, tot) || !mem.alloc(&dntl, 1) || !mem.alloc(&dnte, 1) || !mem.alloc(&ddesc, nc) ||
+      !mem.alloc(&dst, nc) || !mem.alloc(&dtl, ntl) || !mem.alloc(&dte, nte))
+    return fail(ctx, "hipMalloc failed (lite qualification)");
+  hipStream_t st = ctx->stream;
+  DSR_CHECK(ctx, hipMemcpyAsync(dc, cand.data(), sizeof(float4) * tot, hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(dz, hz.data(), sizeof(float) * hz.size(), hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(ddesc, hd.data(), sizeof(ObjDesc) * nc, hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(dst, hs.data(), sizeof(ObjState) * nc, hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(dtl, tl.data(), sizeof(Tile) * ntl, hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(dte, te.data(), sizeof(Tile) * nte, hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(dntl, &ntl, sizeof(int), hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(dnte, &nte, sizeof(int), hipMemcpyHostToDevice, st));
+  DSR_CHECK(ctx, hipMemsetAsync(dref, 0, tot, st));
+  DSR_CHECK(ctx, hipMemsetAsync(ddead, 0, sizeof(int) * tot, st));
+  const DevDecoder& D = dec->D;
+  fold_codes(st, D, dz, nc, db0, db4);
+  ErtArgs E{};
+  E.dead = ddead;
+  E.M = 1;
+  E.nth = -PROBE_TH;
+  E.st = dst;
+  E.refine = dref;
+  E.lag = lite_lag(false);
+  E.audit = 0;
+  E.shell = 1.0f;
+  E.audit_log2 = 7;
+  E.perturb = 0.0f;
+  E.diag = nullptr;
+  launch_lite(st, ctx->n_cu, D, {dtl, dntl, ddesc, dc, db0, db4, dl, E});
+  // against the split-fp16 exact pass a lite batch runs (fwd_kernel(12)), whatever a test's
+  // DSR_FWD_VARIANT selects: the XCD soft-sync variants (bit 0) need a sync counter this launch
+  // has not got, and batches on them never run the lite pass anyway (ADVICE r4)
+  FwdQuery exact{dte, dnte, ddesc, dc, db0, db4, de};
+  exact.kernel = fwd_kernel(12).kernel;
+  launch_fwd(st, ctx->n_cu, D, exact);
+  DSR_CHECK(ctx, hipGetLastError());
+  std::vector<float> yl(tot), ye(tot);
+  DSR_CHECK(ctx, hipMemcpyAsync(yl.data(), dl, sizeof(float) * tot, hipMemcpyDeviceToHost, st));
+  DSR_CHECK(ctx, hipMemcpyAsync(ye.data(), de, sizeof(float) * tot, hipMemcpyDeviceToHost, st));
+  DSR_CHECK(ctx, hipStreamSynchronize(st));
+  double ratio = 0.0, near = 0.0, all = 0.0;
+  for (int i = 0; i < tot; ++i) {
+    const double e = ye[i], d = std::fabs((double)yl[i] - e);
+    if (!std::isfinite(e) || !(d == d)) {          // an overflowing or NaN lite value: not eligible
+      ratio = INFINITY;
+      all = INFINITY;
+      continue;
+    }
+    all = std::max(all, d);
+    if (std::fabs(e) < 0.1) near = std::max(near, d);
+    ratio = std::max(ratio, d / std::max((double)PROBE_FLOOR, std::fabs(std::fabs(e) - (double)PROBE_TH)));
+  }
+  dsr_decoder_info& I = dec->info;
+  I.code_len = dec->code_len;
+  I.lite_probe_ratio = ratio;
+  I.lite_probe_max_err = near;
+  I.lite_probe_max_err_all = all;
+  I.lite_eligible = (ratio <= PROBE_MAX_RATIO && near <= PROBE_MAX_RATIO * PROBE_FLOOR) ? 1 : 0;
+  I.probe_points = n;
+  I.probe_codes = nc;
+  I.probe_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
 int dsr_decoder_load(dsr_ctx* ctx, const dsr_decoder_desc* d, const float* w, size_t n_floats,
                      dsr_decoder** out) {
   if (!ctx || !d || !w || !out) return fail(ctx, "null argument");
@@ -751,11 +925,7 @@ int dsr_decoder_load(dsr_ctx* ctx, const dsr_decoder_desc* d, const float* w, si
   int hf16[8] = {-1}, sw16[8] = {0};
   // the packs' lo pieces by error feedback against each GEMM's inputs at a probe set (pack_frag16)
   const int K3b = l3 <= 448 ? 448 : 512;
-#ifndef DSR_EXP_NOFB
   const DecoderProbe probe = decoder_probe(od, id, W, B, LG, LB, L, l3, XA, K4, K3b, d->use_tanh, true);
-#else   // A/B: lo pieces to nearest
-  const DecoderProbe probe;
-#endif
   for (int l = 1; l <= 7; ++l) {
     std::vector<_Float16> v16;
     if (l == 3) {
@@ -930,6 +1100,12 @@ int dsr_decoder_free(dsr_ctx* ctx, dsr_decoder* dec) {
   return 0;
 }
 
+int dsr_decoder_info_get(const dsr_decoder* dec, dsr_decoder_info* info) {
+  if (!dec || !info) return -2;
+  *info = dec->info;
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // batches
 // ------------------------------------------------------------------------------------
@@ -1076,7 +1252,19 @@ int dsr_batch_destroy(dsr_batch* b) {
   return 0;
 }
 
-static bool graph_enabled();
+// the one owner of a batch under construction: a failure exit destroys it after fail() has set the
+// error (dsr_batch_destroy never writes it); success releases it to the caller
+namespace {   // (internal linkage: the library exports no symbol for the owner)
+struct BatchDeleter {
+  void operator()(dsr_batch* b) const { dsr_batch_destroy(b); }
+};
+}  // namespace
+using BatchOwner = std::unique_ptr<dsr_batch, BatchDeleter>;
+
+static bool graph_enabled() {        // DSR_GRAPH=1: replay re-run batches as hipGraphs
+  const char* ge = getenv("DSR_GRAPH");
+  return ge && atoi(ge) != 0;
+}
 
 static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p,
                              int n_obj, const dsr_object_in* in, bool trace, dsr_batch** out,
@@ -1091,7 +1279,8 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
   if (p->num_iterations < 0) return fail(ctx, "num_iterations < 0");
   if (int rc = decoder_ready(ctx, dec)) return rc;
   hipSetDevice(ctx->device);
-  auto* b = new dsr_batch();
+  BatchOwner owner(new dsr_batch());
+  dsr_batch* b = owner.get();
   b->ctx = ctx;
   b->dec = dec;
   b->hooks = test_hooks();
@@ -1146,10 +1335,7 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
     }
     if (dec->D.ln_mask)
       for (int g = 0; g < G; ++g)
-        if (!ln_workspace(ctx, g)) {
-          dsr_batch_destroy(b);
-          return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
-        }
+        if (!ln_workspace(ctx, g)) return fail(ctx, "hipMalloc failed (LayerNorm workspace)");
   }
   // Every group's slices of the per-ray / per-sample / per-point / per-slot buffers start on
   // a fresh 256 B line (zero padding between groups): the groups' kernels run concurrently on
@@ -1180,19 +1366,15 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
     // Empty inputs are the reference's numeric failures, not errors: no surface points make
     // the sdf loss a mean of nothing (NaN, optimizer.py:137), no rays leave < 10 in-ball
     // samples (loss.py:86-88) — is_good = False, loss 0., exactly as there (golden F10)
-    if (x.n_pts < 0 || (x.n_pts > 0 && !x.pts)) { dsr_batch_destroy(b); return fail(ctx, "bad surface points"); }
-    if (x.n_rays < 0 || (x.n_rays > 0 && !x.rays)) { dsr_batch_destroy(b); return fail(ctx, "bad rays"); }
-    if (x.n_depth < 0 || x.n_depth > x.n_rays || (x.n_depth > 0 && !x.depth)) {
-      dsr_batch_destroy(b);
+    if (x.n_pts < 0 || (x.n_pts > 0 && !x.pts)) return fail(ctx, "bad surface points");
+    if (x.n_rays < 0 || (x.n_rays > 0 && !x.rays)) return fail(ctx, "bad rays");
+    if (x.n_depth < 0 || x.n_depth > x.n_rays || (x.n_depth > 0 && !x.depth))
       return fail(ctx, "depth must hold at most n_rays foreground values");
-    }
     // device offsets and tile tables are 32-bit: a batch holds at most 2^31 - 1 ray samples
     // plus surface points (HBM runs out first with kept masks, ~580 B per sample; without
     // them ~70 B per sample would let a batch pass the limit) — split larger jobs
-    if ((long long)x.n_rays * M + cand_off + x.n_pts + pts_off > (long long)INT_MAX) {
-      dsr_batch_destroy(b);
+    if ((long long)x.n_rays * M + cand_off + x.n_pts + pts_off > (long long)INT_MAX)
       return fail(ctx, "batch too large: more than 2^31 - 1 ray samples + surface points (split it)");
-    }
     ObjDesc d{};
     d.pts_off = pts_off; d.n_pts = x.n_pts;
     d.ray_off = ray_off; d.n_rays = x.n_rays; d.n_fg = x.n_depth;
@@ -1221,7 +1403,7 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
   b->jac_tile_cap = slot_off;
   int rc = 0;
 #define ALLOC(ptr, bytes) \
-  if ((rc = batch_alloc(b, (void**)&(ptr), (bytes))) != 0) { dsr_batch_destroy(b); return rc; }
+  if ((rc = batch_alloc(b, (void**)&(ptr), (bytes))) != 0) return rc;
   ALLOC(b->desc, sizeof(ObjDesc) * n_obj);
   ALLOC(b->st, sizeof(ObjState) * n_obj);
   ALLOC(b->zbuf, sizeof(float) * CODE * n_obj);
@@ -1340,10 +1522,8 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
     ALLOC(b->refine, (size_t)std::max(1, cand_off));
     ALLOC(b->rbits, sizeof(uint64_t) * (size_t)std::max(1, ray_off));
     ALLOC(b->abits, sizeof(uint64_t) * (size_t)std::max(1, ray_off));
-    if (hipMemsetAsync(b->refine, 0, (size_t)std::max(1, cand_off), ctx->stream) != hipSuccess) {
-      dsr_batch_destroy(b);
+    if (hipMemsetAsync(b->refine, 0, (size_t)std::max(1, cand_off), ctx->stream) != hipSuccess)
       return fail(ctx, "hipMemset failed");
-    }
   }
   ALLOC(b->kres, sizeof(float) * (size_t)cand_off);
   ALLOC(b->kst, sizeof(float4) * (size_t)cand_off);
@@ -1375,10 +1555,8 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
     ALLOC(gr.och, sizeof(int2) * och.size());
     if (!rch.empty() &&
         (hipMemcpy(gr.rchunks, rch.data(), sizeof(RenderChunk) * rch.size(), hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(gr.och, och.data(), sizeof(int2) * och.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-      dsr_batch_destroy(b);
+         hipMemcpy(gr.och, och.data(), sizeof(int2) * och.size(), hipMemcpyHostToDevice) != hipSuccess))
       return fail(ctx, "hipMemcpy (render chunks) failed");
-    }
   }
   ALLOC(b->slots, sizeof(float) * SLOT_FLOATS * (size_t)slot_off);
   ALLOC(b->sred, sizeof(float) * SRED_STRIDE * (size_t)n_obj);
@@ -1417,10 +1595,8 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
       !up(b->rays, hrays.data(), sizeof(float) * hrays.size()) ||
       !up(b->dobs, hdobs.data(), sizeof(float) * hdobs.size()) ||
       (views && (!up(b->tie, htie.data(), sizeof(int2) * htie.size()) ||
-                 !up(b->cview, cview, sizeof(float) * 16 * n_obj)))) {
-    dsr_batch_destroy(b);
+                 !up(b->cview, cview, sizeof(float) * 16 * n_obj))))
     return fail(ctx, "hipMemcpy (inputs) failed");
-  }
   if (trace) {
     hipMemsetAsync(b->tr_H, 0, sizeof(float) * TRACE_H_STRIDE * std::max(1, b->iters) * n_obj, ctx->stream);
     hipMemsetAsync(b->tr_v, 0, sizeof(float) * TRACE_V_STRIDE * std::max(1, b->iters) * n_obj, ctx->stream);
@@ -1430,14 +1606,12 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
   b->ev.resize((size_t)std::max(1, b->loop_iters) * b->groups.size() * ev_per_iter(b) + 2);
   b->join_ev.resize(b->groups.size());
   for (auto& e : b->ev)
-    if (pool_event(ctx, &e, true) != hipSuccess) { dsr_batch_destroy(b); return fail(ctx, "hipEventCreate failed"); }
+    if (pool_event(ctx, &e, true) != hipSuccess) return fail(ctx, "hipEventCreate failed");
   for (auto& e : b->join_ev)
-    if (pool_event(ctx, &e, false) != hipSuccess) { dsr_batch_destroy(b); return fail(ctx, "hipEventCreate failed"); }
-  if (pool_event(ctx, &b->done_ev, false) != hipSuccess || pool_event(ctx, &b->fork_ev, false) != hipSuccess) {
-    dsr_batch_destroy(b);
+    if (pool_event(ctx, &e, false) != hipSuccess) return fail(ctx, "hipEventCreate failed");
+  if (pool_event(ctx, &b->done_ev, false) != hipSuccess || pool_event(ctx, &b->fork_ev, false) != hipSuccess)
     return fail(ctx, "hipEventCreate failed");
-  }
-  *out = b;
+  *out = owner.release();
   return 0;
 }
 
@@ -1471,6 +1645,7 @@ int dsr_batch_create_capacity(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_op
   dsr_batch* b = nullptr;
   int rc = batch_create_impl(ctx, dec, p, max_obj, in.data(), false, &b, (flags & DSR_BATCH_GRAPH) != 0);
   if (rc) return rc;
+  BatchOwner owner(b);
   b->capacity = true;
   b->cap_graph = (flags & DSR_BATCH_GRAPH) != 0;
   b->max_pts = max_pts;
@@ -1487,22 +1662,15 @@ int dsr_batch_create_capacity(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_op
     sg.bytes = std::max<size_t>(kv.second, 4);
     if (hipHostMalloc(&sg.host, sg.bytes, hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
-      dsr_batch_destroy(b);
       return fail(ctx, "hipHostMalloc failed (capacity batch staging)");
     }
     std::memset(sg.host, 0, sg.bytes);
     b->stage.push_back(sg);
   }
-  if (pool_event(ctx, &b->up_ev, false) != hipSuccess) {
-    dsr_batch_destroy(b);
-    return fail(ctx, "hipEventCreate failed");
-  }
+  if (pool_event(ctx, &b->up_ev, false) != hipSuccess) return fail(ctx, "hipEventCreate failed");
   rc = dsr_batch_refill(b, 0, nullptr);          // every slot empty until the first fill
-  if (rc) {
-    dsr_batch_destroy(b);
-    return rc;
-  }
-  *out = b;
+  if (rc) return rc;
+  *out = owner.release();
   return 0;
 }
 
@@ -1858,166 +2026,6 @@ int dsr_batch_frame_info(dsr_batch* b, dsr_frame_det_out* out) {
   return 0;
 }
 
-static int batch_enqueue(dsr_batch* b, bool timing = true);
-static int batch_finish(dsr_batch* b);
-
-static int jac_variant() {
-  const char* e = hook_env("DSR_JAC_VARIANT");
-  return e ? atoi(e) : 12;
-}
-
-// dsr_batch_run: with DSR_GRAPH=1 the first run of a batch is enqueued eagerly and from
-// the second on (a re-run batch: streaming keyframes, config 5) the whole launch sequence —
-// ~6 + 3 x passes launches per iteration and object group; one group by default under
-// DSR_GRAPH=1 (batch_create_impl) — is captured once into a hipGraph and replayed with one
-// launch; dsr_batch_graph captures up front.  A
-// replayed run records only its total time (kernel events stay out of the graph: HIP
-// cannot time events recorded inside one), so dsr_batch_stats reports no kernel times.
-static bool graph_enabled() {        // DSR_GRAPH=1: replay re-run batches as hipGraphs
-  const char* ge = getenv("DSR_GRAPH");
-  return ge && atoi(ge) != 0;
-}
-static long graph_key() { return ((long)fwd_variant() * 100000 + jac_variant()) * 10 + split_ring(); }
-
-static int batch_capture(dsr_batch* b) {
-  dsr_ctx* ctx = b->ctx;
-  if (b->graph) {
-    hipGraphExecDestroy(b->graph);
-    b->graph = nullptr;
-  }
-  hipGraph_t g = nullptr;
-  DSR_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  const int rc = batch_enqueue(b, false);      // kernel timing events stay out of the graph
-  const hipError_t ec = hipStreamEndCapture(ctx->stream, &g);
-  if (rc) {
-    if (g) hipGraphDestroy(g);
-    return rc;
-  }
-  DSR_CHECK(ctx, ec);
-  const hipError_t ei = hipGraphInstantiate(&b->graph, g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  DSR_CHECK(ctx, ei);
-  b->graph_key = graph_key();
-  ++b->captures;
-  return 0;
-}
-
-int dsr_batch_graph(dsr_batch* b) {
-  if (!b) return -2;
-  std::lock_guard<std::recursive_mutex> run(b->ctx->run_mu);
-  hipSetDevice(b->ctx->device);
-  if (!graph_enabled() && !b->cap_graph) return 0;
-  b->runs = std::max(b->runs, 1);
-  return batch_capture(b);
-}
-
-static int batch_launch(dsr_batch* b) {
-  dsr_ctx* ctx = b->ctx;
-  if (b->capacity && b->n_active == 0) return fail(ctx, "capacity batch holds no objects (dsr_batch_refill)");
-  // a DSR_BATCH_GRAPH capacity batch replays from its first run (its refills keep every kernel
-  // argument); other batches under DSR_GRAPH=1 run eagerly once, then replay
-  const bool first_eager = !b->cap_graph;
-  if (!(graph_enabled() || b->cap_graph) || (b->runs++ == 0 && first_eager)) {
-    const int rc = batch_enqueue(b);
-    if (rc) return rc;
-    b->ran = true;
-    b->timed = true;
-    return 0;
-  }
-  if (!b->graph || b->graph_key != graph_key()) {
-    const int rc = batch_capture(b);
-    if (rc) return rc;
-  }
-  DSR_CHECK(ctx, hipEventRecord(b->ev[0], ctx->stream));
-  // poison the out-records first: a replay's k_finalize (inside the graph) rewrites every one,
-  // so a download that ever saw these bytes would expose work ordered wrongly around the graph
-  // launch (test_graph_replays_never_return_stale_records) instead of returning stale results
-  DSR_CHECK(ctx, hipMemsetAsync(b->out, 0xff, sizeof(dsr_object_out) * b->n_obj, ctx->stream));
-  DSR_CHECK(ctx, hipGraphLaunch(b->graph, ctx->stream));
-  DSR_CHECK(ctx, hipEventRecord(b->ev[1], ctx->stream));
-  ++b->replays;
-  b->spare_run = false;          // a replay runs the regular iterations only (batch_finish)
-  b->ran = true;
-  b->timed = false;
-  return 0;
-}
-
-int dsr_batch_run(dsr_batch* b) {
-  if (!b) return -2;
-  dsr_ctx* ctx = b->ctx;
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  const int rc = batch_launch(b);
-  if (rc) return rc;
-  DSR_CHECK(ctx, hipEventRecord(b->done_ev, ctx->stream));
-  return 0;
-}
-
-static int batch_redo(dsr_batch* b);
-
-int dsr_batch_query(dsr_batch* b) {
-  if (!b) return -2;
-  if (!b->ran) return fail(b->ctx, "batch has not run");
-  std::lock_guard<std::recursive_mutex> run(b->ctx->run_mu);
-  hipSetDevice(b->ctx->device);
-  const hipError_t e = hipEventQuery(b->done_ev);
-  if (e == hipSuccess) {
-    // a pending audit redo is enqueued here and the batch reported as still in flight: the
-    // caller's next query sees it finish (never blocks for a GN iteration)
-    const int rc = batch_redo(b);
-    return rc < 0 ? rc : (rc == 1 ? 0 : 1);
-  }
-  if (e == hipErrorNotReady) return 0;
-  return fail(b->ctx, std::string("hipEventQuery: ") + hipGetErrorString(e));
-}
-
-static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1);
-
-static int batch_enqueue(dsr_batch* b, bool timing) {
-  dsr_ctx* ctx = b->ctx;
-  const int n = b->n_obj;
-  if (timing) DSR_CHECK(ctx, hipEventRecord(b->ev[0], ctx->stream));
-  hipLaunchKernelGGL(k_init_state, dim3(n), dim3(64), 0, ctx->stream, n, b->t_in, b->is_oc, b->z_in, b->st,
-                     b->zbuf, b->iters);
-  DSR_CHECK(ctx, hipMemsetAsync(b->diag, 0, sizeof(int) * STD_INTS, ctx->stream));
-  if (b->n_tied) DSR_CHECK(ctx, hipMemsetAsync(b->fail_view, 0xff, sizeof(int) * b->n_tied, ctx->stream));
-  if (b->tie_multi)               // the views' start poses from their leaders' (before the groups fork)
-    for (const auto& gr : b->groups)
-      hipLaunchKernelGGL(k_views_pose, dim3(gr.nt), dim3(64), 0, ctx->stream, (const int2*)b->tie + gr.t0,
-                         b->st + gr.o0, (const float*)b->cview + (size_t)gr.o0 * 16);
-  b->spare_run = false;
-  return batch_enqueue_iters(b, timing, 0, b->iters);
-}
-
-// The spare iteration (lite + audit): only objects whose iteration an audit discarded
-// (k_solve) are still running after the regular iterations.  It is enqueued on demand once
-// the regular iterations have finished (batch_finish, dsr_batch_query), so a run without
-// violations launches nothing extra; graphs capture the regular iterations only.
-// Returns 1 if the spare iteration was enqueued now, 0 if there is nothing to redo.
-static int batch_redo(dsr_batch* b) {
-  dsr_ctx* ctx = b->ctx;
-  if (b->loop_iters <= b->iters || b->spare_run) return 0;
-  std::vector<ObjState> hs(b->n_obj);
-  DSR_CHECK(ctx, hipMemcpy(hs.data(), b->st, sizeof(ObjState) * hs.size(), hipMemcpyDeviceToHost));
-  bool any = false;
-  for (const ObjState& o : hs) any = any || (o.status == ST_RUNNING && o.lite_redo);
-  if (!any) return 0;
-  b->spare_run = true;
-  const int rc = batch_enqueue_iters(b, b->timed, b->iters, b->loop_iters);
-  if (rc) return rc;
-  DSR_CHECK(ctx, hipEventRecord(b->done_ev, ctx->stream));
-  return 1;
-}
-static int batch_finish(dsr_batch* b) {
-  dsr_ctx* ctx = b->ctx;
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  const int rc = batch_redo(b);
-  if (rc < 0) return rc;
-  if (rc == 1) DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return 0;
-}
-
 static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
   dsr_ctx* ctx = b->ctx;
   hipStream_t s0 = ctx->stream;
@@ -2027,20 +2035,17 @@ static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
   const int grid = ctx->n_cu;
   const int cb = (n + 63) / 64;
   const int fv = fwd_variant();
-  const FwdKernel fwdk = fwd_kernel_for(D, fv);
-  const JacKernel jack = jac_kernel_for(D);
+  const FwdChoice fwdc = fwd_kernel_for(D, fv);
+  const JacChoice jacc = jac_kernel_for(D);
+  const FwdKernel fwdk = fwdc.kernel;
+  const JacKernel jack = jacc.kernel;
   const LiteSchedule& lites = lite_schedule();
   const LiteKernel litek = lites.kernel;
   // (the kernels dispatched, as dsr_batch_stats reports them: fwd_kernel / jac_kernel's choice)
-  {
-    const int fl = fv & 15;
-    const bool known = fl == 1 || fl == 2 || fl == 3 || fl == 6 || fl == 7 || fl == 8 || fl == 12;
-    const int jv = jac_variant();
-    b->ran_fwd = is_variant(D) ? 12 : (known ? fv : (fv & ~15));
-    b->ran_jac = is_variant(D) ? 12 : ((jv == 8 || jv == 12) ? jv : 0);
-    b->ran_lite = b->lite ? lites.number : 0;
-    b->ran_ring = is_variant(D) ? 2 : split_ring();
-  }
+  b->ran_fwd = fwdc.number;
+  b->ran_jac = jacc.number;
+  b->ran_lite = b->lite ? lites.number : 0;
+  b->ran_ring = fwdc.ring;
   const int np = (int)b->passes.size() - 1;
   const size_t epi = ev_per_iter(b);
   const int G = (int)b->groups.size();
@@ -2169,6 +2174,150 @@ static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
   DSR_CHECK(ctx, hipGetLastError());
   if (timing) DSR_CHECK(ctx, hipEventRecord(b->ev[1], s0));
   return 0;
+}
+
+static int batch_enqueue(dsr_batch* b, bool timing = true) {
+  dsr_ctx* ctx = b->ctx;
+  const int n = b->n_obj;
+  if (timing) DSR_CHECK(ctx, hipEventRecord(b->ev[0], ctx->stream));
+  hipLaunchKernelGGL(k_init_state, dim3(n), dim3(64), 0, ctx->stream, n, b->t_in, b->is_oc, b->z_in, b->st,
+                     b->zbuf, b->iters);
+  DSR_CHECK(ctx, hipMemsetAsync(b->diag, 0, sizeof(int) * STD_INTS, ctx->stream));
+  if (b->n_tied) DSR_CHECK(ctx, hipMemsetAsync(b->fail_view, 0xff, sizeof(int) * b->n_tied, ctx->stream));
+  if (b->tie_multi)               // the views' start poses from their leaders' (before the groups fork)
+    for (const auto& gr : b->groups)
+      hipLaunchKernelGGL(k_views_pose, dim3(gr.nt), dim3(64), 0, ctx->stream, (const int2*)b->tie + gr.t0,
+                         b->st + gr.o0, (const float*)b->cview + (size_t)gr.o0 * 16);
+  b->spare_run = false;
+  return batch_enqueue_iters(b, timing, 0, b->iters);
+}
+
+// The spare iteration (lite + audit): only objects whose iteration an audit discarded
+// (k_solve) are still running after the regular iterations.  It is enqueued on demand once
+// the regular iterations have finished (batch_finish, dsr_batch_query), so a run without
+// violations launches nothing extra; graphs capture the regular iterations only.
+// Returns 1 if the spare iteration was enqueued now, 0 if there is nothing to redo.
+static int batch_redo(dsr_batch* b) {
+  dsr_ctx* ctx = b->ctx;
+  if (b->loop_iters <= b->iters || b->spare_run) return 0;
+  std::vector<ObjState> hs(b->n_obj);
+  DSR_CHECK(ctx, hipMemcpy(hs.data(), b->st, sizeof(ObjState) * hs.size(), hipMemcpyDeviceToHost));
+  bool any = false;
+  for (const ObjState& o : hs) any = any || (o.status == ST_RUNNING && o.lite_redo);
+  if (!any) return 0;
+  b->spare_run = true;
+  const int rc = batch_enqueue_iters(b, b->timed, b->iters, b->loop_iters);
+  if (rc) return rc;
+  DSR_CHECK(ctx, hipEventRecord(b->done_ev, ctx->stream));
+  return 1;
+}
+static int batch_finish(dsr_batch* b) {
+  dsr_ctx* ctx = b->ctx;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  const int rc = batch_redo(b);
+  if (rc < 0) return rc;
+  if (rc == 1) DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// dsr_batch_run: with DSR_GRAPH=1 the first run of a batch is enqueued eagerly and from
+// the second on (a re-run batch: streaming keyframes, config 5) the whole launch sequence —
+// ~6 + 3 x passes launches per iteration and object group; one group by default under
+// DSR_GRAPH=1 (batch_create_impl) — is captured once into a hipGraph and replayed with one
+// launch; dsr_batch_graph captures up front.  A
+// replayed run records only its total time (kernel events stay out of the graph: HIP
+// cannot time events recorded inside one), so dsr_batch_stats reports no kernel times.
+static long graph_key() { return ((long)fwd_variant() * 100000 + jac_variant()) * 10 + split_ring(); }
+
+static int batch_capture(dsr_batch* b) {
+  dsr_ctx* ctx = b->ctx;
+  if (b->graph) {
+    hipGraphExecDestroy(b->graph);
+    b->graph = nullptr;
+  }
+  hipGraph_t g = nullptr;
+  DSR_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+  const int rc = batch_enqueue(b, false);      // kernel timing events stay out of the graph
+  const hipError_t ec = hipStreamEndCapture(ctx->stream, &g);
+  if (rc) {
+    if (g) hipGraphDestroy(g);
+    return rc;
+  }
+  DSR_CHECK(ctx, ec);
+  const hipError_t ei = hipGraphInstantiate(&b->graph, g, nullptr, nullptr, 0);
+  hipGraphDestroy(g);
+  DSR_CHECK(ctx, ei);
+  b->graph_key = graph_key();
+  ++b->captures;
+  return 0;
+}
+
+static int batch_launch(dsr_batch* b) {
+  dsr_ctx* ctx = b->ctx;
+  if (b->capacity && b->n_active == 0) return fail(ctx, "capacity batch holds no objects (dsr_batch_refill)");
+  // a DSR_BATCH_GRAPH capacity batch replays from its first run (its refills keep every kernel
+  // argument); other batches under DSR_GRAPH=1 run eagerly once, then replay
+  const bool first_eager = !b->cap_graph;
+  if (!(graph_enabled() || b->cap_graph) || (b->runs++ == 0 && first_eager)) {
+    const int rc = batch_enqueue(b);
+    if (rc) return rc;
+    b->ran = true;
+    b->timed = true;
+    return 0;
+  }
+  if (!b->graph || b->graph_key != graph_key()) {
+    const int rc = batch_capture(b);
+    if (rc) return rc;
+  }
+  DSR_CHECK(ctx, hipEventRecord(b->ev[0], ctx->stream));
+  // poison the out-records first: a replay's k_finalize (inside the graph) rewrites every one,
+  // so a download that ever saw these bytes would expose work ordered wrongly around the graph
+  // launch (test_graph_replays_never_return_stale_records) instead of returning stale results
+  DSR_CHECK(ctx, hipMemsetAsync(b->out, 0xff, sizeof(dsr_object_out) * b->n_obj, ctx->stream));
+  DSR_CHECK(ctx, hipGraphLaunch(b->graph, ctx->stream));
+  DSR_CHECK(ctx, hipEventRecord(b->ev[1], ctx->stream));
+  ++b->replays;
+  b->spare_run = false;          // a replay runs the regular iterations only (batch_finish)
+  b->ran = true;
+  b->timed = false;
+  return 0;
+}
+
+int dsr_batch_graph(dsr_batch* b) {
+  if (!b) return -2;
+  std::lock_guard<std::recursive_mutex> run(b->ctx->run_mu);
+  hipSetDevice(b->ctx->device);
+  if (!graph_enabled() && !b->cap_graph) return 0;
+  b->runs = std::max(b->runs, 1);
+  return batch_capture(b);
+}
+
+int dsr_batch_run(dsr_batch* b) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const int rc = batch_launch(b);
+  if (rc) return rc;
+  DSR_CHECK(ctx, hipEventRecord(b->done_ev, ctx->stream));
+  return 0;
+}
+
+int dsr_batch_query(dsr_batch* b) {
+  if (!b) return -2;
+  if (!b->ran) return fail(b->ctx, "batch has not run");
+  std::lock_guard<std::recursive_mutex> run(b->ctx->run_mu);
+  hipSetDevice(b->ctx->device);
+  const hipError_t e = hipEventQuery(b->done_ev);
+  if (e == hipSuccess) {
+    // a pending audit redo is enqueued here and the batch reported as still in flight: the
+    // caller's next query sees it finish (never blocks for a GN iteration)
+    const int rc = batch_redo(b);
+    return rc < 0 ? rc : (rc == 1 ? 0 : 1);
+  }
+  if (e == hipErrorNotReady) return 0;
+  return fail(b->ctx, std::string("hipEventQuery: ") + hipGetErrorString(e));
 }
 
 int dsr_batch_sync(dsr_batch* b) {
@@ -2327,8 +2476,8 @@ int dsr_batch_lite_diag(dsr_batch* b, int* rec, int n) {
 // dev[i] * maxn + slot[i] of the gathered buffer (dsr_gather_layout).  RCCL is loaded at run time;
 // when it is missing or its communicator cannot be built (e.g. two contexts on one device), the
 // records are gathered through host memory instead, and *path says which route ran.
-extern "C" int dsr_gather_layout(int n_obj, const dsr_object_in* in, int num_depth_samples, int n_dev, int* dev,
-                                 int* slot, int* maxn) {
+int dsr_gather_layout(int n_obj, const dsr_object_in* in, int num_depth_samples, int n_dev, int* dev, int* slot,
+                      int* maxn) {
   if (n_obj <= 0 || !in || n_dev <= 0 || !dev || !slot || !maxn) return -2;
   std::vector<int> order(n_obj);
   for (int i = 0; i < n_obj; ++i) order[i] = i;
@@ -2346,7 +2495,8 @@ extern "C" int dsr_gather_layout(int n_obj, const dsr_object_in* in, int num_dep
   return 0;
 }
 
-extern "C++" {   // (inside the file's extern "C" block: C++ linkage for the helpers)
+}  // extern "C" (the RCCL loader is C++: the block reopens after it)
+
 namespace {
 // RCCL entry points, resolved from librccl at first use (no link-time dependency: a host
 // without RCCL still loads libdsr and gathers through host memory)
@@ -2402,11 +2552,12 @@ const std::vector<ncclComm_t>* comms_for(const std::vector<int>& devs, std::stri
   return &it->second;
 }
 }  // namespace
-}  // extern "C++"
 
-extern "C" int dsr_reconstruct_multi_ex(dsr_ctx* const* ctxs, const dsr_decoder* const* decs, int n_dev,
-                                        const dsr_optim_params* p, int n_obj, const dsr_object_in* in,
-                                        dsr_object_out* out, int* path) {
+extern "C" {
+
+int dsr_reconstruct_multi_ex(dsr_ctx* const* ctxs, const dsr_decoder* const* decs, int n_dev,
+                             const dsr_optim_params* p, int n_obj, const dsr_object_in* in, dsr_object_out* out,
+                             int* path) {
   if (!ctxs || !decs || n_dev <= 0 || !ctxs[0]) return -2;
   dsr_ctx* c0 = ctxs[0];
   if (!p || !out || (n_obj > 0 && !in)) return fail(c0, "null argument");
@@ -2652,177 +2803,46 @@ int dsr_reconstruct_views(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_
 }
 
 // ------------------------------------------------------------------------------------
-// raw decoder queries (dsr_sdf_eval)
-// ------------------------------------------------------------------------------------
-__global__ void k_fold_code(DevDecoder D, const float* __restrict__ z, float* __restrict__ bias0f,
-                            float* __restrict__ bias4f) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= HID) return;
-  float s0 = 0.f, s4 = 0.f;
-  for (int k = 0; k < CODE; ++k) {
-    s0 = __builtin_fmaf(D.W0z[k * HID + n], z[k], s0);
-    s4 = __builtin_fmaf(D.W4z[k * HID + n], z[k], s4);
-  }
-  bias0f[n] = D.bias[0][n] + s0;
-  bias4f[n] = D.bias[4][n] + s4;
-}
-// the bias folds of n codes (64 floats each, back to back) into b0 / b4 (HID floats each)
-static void fold_codes(hipStream_t s, const DevDecoder& D, const float* codes, int n, float* b0, float* b4) {
-  for (int i = 0; i < n; ++i)
-    hipLaunchKernelGGL(k_fold_code, dim3(HID / 256), dim3(256), 0, s, D, codes + (size_t)i * CODE, b0 + (size_t)i * HID,
-                       b4 + (size_t)i * HID);
-}
-
-// ------------------------------------------------------------------------------------
-// load-time qualification of the lite pass (include/dsr.h: dsr_decoder_info)
-// ------------------------------------------------------------------------------------
-// The lite pass classifies ray samples with one fp16 product; the per-object margin and the
-// audit (DESIGN.md §3.4) guard it at run time, but their evidence is empirical: a decoder with
-// larger weights or activations has larger fp16 errors.  So before any batch trusts the lite
-// pass with a loaded decoder, the decoder decodes a fixed probe set through both passes — the
-// same kernels, tiles and bias fold a batch uses — and the lite error is measured against the
-// distance of each exact value to its nearest class boundary (full <= -th < band < th <=
-// empty, th = 0.01, loss_utils.py:40-48, loss.py:98-102), floored at the margin floor 0.002, and
-// against the floor itself near the surface (|exact| < 0.1, where the band and the audit shell
-// lie).  Above half of either anywhere, the decoder is lite-ineligible and every batch decodes
-// exactly.
-static constexpr int PROBE_POINTS = 65536, PROBE_CODES = 4;
-static constexpr float PROBE_TH = 0.01f, PROBE_FLOOR = 0.002f, PROBE_MAX_RATIO = 0.5f;
-
-static int decoder_qualify(dsr_ctx* ctx, dsr_decoder* dec) {
-  const auto t0 = std::chrono::steady_clock::now();
-  if (dec->D.xyz_all || dec->D.use_tanh || dec->D.ln_mask) {   // the lite kernels: the shipped topology only
-    dsr_decoder_info& I = dec->info;
-    I.code_len = dec->code_len;
-    I.lite_eligible = 0;
-    I.lite_probe_ratio = I.lite_probe_max_err = I.lite_probe_max_err_all = NAN;
-    I.probe_points = I.probe_codes = 0;
-    I.probe_ms = 0.0;
-    return 0;
-  }
-  const int n = PROBE_POINTS, nc = PROBE_CODES, tot = n * nc;
-  uint64_t s = 0x9E3779B97F4A7C15ull;           // fixed LCG: the probe set is part of the contract
-  auto u01 = [&]() {
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(s >> 11) * (1.0 / 9007199254740992.0);
-  };
-  std::vector<float4> cand(tot);
-  for (int i = 0; i < n;) {                     // uniform in the unit ball (rejection from the cube)
-    const double x = 2 * u01() - 1, y = 2 * u01() - 1, z = 2 * u01() - 1;
-    if (x * x + y * y + z * z >= 1.0) continue;
-    for (int c = 0; c < nc; ++c) {
-      int idx = i;
-      float fi;
-      std::memcpy(&fi, &idx, sizeof(float));
-      cand[(size_t)c * n + i] = make_float4((float)x, (float)y, (float)z, fi);
-    }
-    ++i;
-  }
-  static const float scale[PROBE_CODES] = {0.0f, 0.1f, 0.3f, 1.0f};
-  std::vector<float> hz((size_t)nc * CODE);
-  for (int c = 0; c < nc; ++c)
-    for (int k = 0; k < CODE; ++k) {               // Box-Muller
-      const double r = std::sqrt(-2.0 * std::log(1.0 - u01())), t = 2.0 * M_PI * u01();
-      hz[(size_t)c * CODE + k] = (float)(scale[c] * r * std::cos(t));
-    }
-  std::vector<ObjDesc> hd(nc);
-  std::vector<ObjState> hs(nc);
-  std::vector<Tile> tl, te;
-  for (int c = 0; c < nc; ++c) {
-    hd[c] = ObjDesc{};
-    hd[c].ray_off = c * n;
-    hd[c].n_rays = n;
-    hd[c].cand_off = c * n;
-    std::memset(&hs[c], 0, sizeof(ObjState));    // lite_margin 0: flags are not used here
-    for (int t = 0; t * LTILE < n; ++t) tl.push_back(Tile{c, 0, t * LTILE, std::min(LTILE, n - t * LTILE)});
-    for (int t = 0; t * TILE < n; ++t) te.push_back(Tile{c, 0, t * TILE, std::min(TILE, n - t * TILE)});
-  }
-  const int ntl = (int)tl.size(), nte = (int)te.size();
-  DevArena mem;
-  float4* dc = nullptr;
-  float *dl = nullptr, *de = nullptr, *dz = nullptr, *db0 = nullptr, *db4 = nullptr;
-  unsigned char* dref = nullptr;
-  int *ddead = nullptr, *dntl = nullptr, *dnte = nullptr;
-  ObjDesc* ddesc = nullptr;
-  ObjState* dst = nullptr;
-  Tile *dtl = nullptr, *dte = nullptr;
-  if (!mem.alloc(&dc, tot) || !mem.alloc(&dl, tot) || !mem.alloc(&de, tot) || !mem.alloc(&dz, hz.size()) ||
-      !mem.alloc(&db0, HID * nc) || !mem.alloc(&db4, HID * nc) || !mem.alloc(&dref, tot) ||
-      !mem.alloc(&ddead, tot) || !mem.alloc(&dntl, 1) || !mem.alloc(&dnte, 1) || !mem.alloc(&ddesc, nc) ||
-      !mem.alloc(&dst, nc) || !mem.alloc(&dtl, ntl) || !mem.alloc(&dte, nte))
-    return fail(ctx, "hipMalloc failed (lite qualification)");
-  hipStream_t st = ctx->stream;
-  DSR_CHECK(ctx, hipMemcpyAsync(dc, cand.data(), sizeof(float4) * tot, hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(dz, hz.data(), sizeof(float) * hz.size(), hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(ddesc, hd.data(), sizeof(ObjDesc) * nc, hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(dst, hs.data(), sizeof(ObjState) * nc, hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(dtl, tl.data(), sizeof(Tile) * ntl, hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(dte, te.data(), sizeof(Tile) * nte, hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(dntl, &ntl, sizeof(int), hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(dnte, &nte, sizeof(int), hipMemcpyHostToDevice, st));
-  DSR_CHECK(ctx, hipMemsetAsync(dref, 0, tot, st));
-  DSR_CHECK(ctx, hipMemsetAsync(ddead, 0, sizeof(int) * tot, st));
-  const DevDecoder& D = dec->D;
-  fold_codes(st, D, dz, nc, db0, db4);
-  ErtArgs E{};
-  E.dead = ddead;
-  E.M = 1;
-  E.nth = -PROBE_TH;
-  E.st = dst;
-  E.refine = dref;
-  E.lag = lite_lag(false);
-  E.audit = 0;
-  E.shell = 1.0f;
-  E.audit_log2 = 7;
-  E.perturb = 0.0f;
-  E.diag = nullptr;
-  launch_lite(st, ctx->n_cu, D, {dtl, dntl, ddesc, dc, db0, db4, dl, E});
-  // against the split-fp16 exact pass a lite batch runs (fwd_kernel(12)), whatever a test's
-  // DSR_FWD_VARIANT selects: the XCD soft-sync variants (bit 0) need a sync counter this launch
-  // has not got, and batches on them never run the lite pass anyway (ADVICE r4)
-  FwdQuery exact{dte, dnte, ddesc, dc, db0, db4, de};
-  exact.kernel = fwd_kernel(12);
-  launch_fwd(st, ctx->n_cu, D, exact);
-  DSR_CHECK(ctx, hipGetLastError());
-  std::vector<float> yl(tot), ye(tot);
-  DSR_CHECK(ctx, hipMemcpyAsync(yl.data(), dl, sizeof(float) * tot, hipMemcpyDeviceToHost, st));
-  DSR_CHECK(ctx, hipMemcpyAsync(ye.data(), de, sizeof(float) * tot, hipMemcpyDeviceToHost, st));
-  DSR_CHECK(ctx, hipStreamSynchronize(st));
-  double ratio = 0.0, near = 0.0, all = 0.0;
-  for (int i = 0; i < tot; ++i) {
-    const double e = ye[i], d = std::fabs((double)yl[i] - e);
-    if (!std::isfinite(e) || !(d == d)) {          // an overflowing or NaN lite value: not eligible
-      ratio = INFINITY;
-      all = INFINITY;
-      continue;
-    }
-    all = std::max(all, d);
-    if (std::fabs(e) < 0.1) near = std::max(near, d);
-    ratio = std::max(ratio, d / std::max((double)PROBE_FLOOR, std::fabs(std::fabs(e) - (double)PROBE_TH)));
-  }
-  dsr_decoder_info& I = dec->info;
-  I.code_len = dec->code_len;
-  I.lite_probe_ratio = ratio;
-  I.lite_probe_max_err = near;
-  I.lite_probe_max_err_all = all;
-  I.lite_eligible = (ratio <= PROBE_MAX_RATIO && near <= PROBE_MAX_RATIO * PROBE_FLOOR) ? 1 : 0;
-  I.probe_points = n;
-  I.probe_codes = nc;
-  I.probe_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return 0;
-}
-
-int dsr_decoder_info_get(const dsr_decoder* dec, dsr_decoder_info* info) {
-  if (!dec || !info) return -2;
-  *info = dec->info;
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------
 // mesh extraction (MeshExtractor, optimizer.py:216-233; utils.py:119-140)
 // ------------------------------------------------------------------------------------
-struct MeshBatch;
-static void mesh_batch_free(MeshBatch* b);
+// S slots of everything a mesh needs; a call runs its codes in passes of up to S.  S grows with
+// the calls' code counts up to MESH_MAX_SLOTS and while one pass's buffers stay within
+// MESH_BUDGET (the marching-cubes buffers hold the worst case of every slot: ~270 MB per slot at
+// 128^3, so 6 slots there; 16 up to 96^3).
+static constexpr int MESH_MAX_SLOTS = 16;
+static constexpr size_t MESH_BUDGET = (size_t)2 << 30;
+static constexpr float MESH_MARGIN = 0.01f;      // §3.4's first-iteration margin
+
+struct MeshBatch {
+  int S = 0, np = 0, ntl = 0, n_rb = 0;
+  int last_ns = 0;             // slots of the last pass (dsr_mesher_peek)
+  bool last_sign = false;
+  DevArena mem;
+  float4* pts = nullptr;       // the grid, once per slot (the kernels index it by ObjDesc.cand_off)
+  float *lite = nullptr, *vol = nullptr, *codes = nullptr, *b0 = nullptr, *b4 = nullptr, *verts = nullptr;
+  unsigned char *refine = nullptr, *tflag = nullptr;
+  int *flag = nullptr, *vidx = nullptr, *ntri = nullptr, *toff = nullptr, *bsum = nullptr, *faces = nullptr;
+  int *tmark = nullptr, *tpos = nullptr;
+  Tile *ltiles = nullptr, *atiles = nullptr, *etiles = nullptr, *rtiles = nullptr;
+  ObjDesc* desc = nullptr;
+  ObjState* st = nullptr;
+  // one record of ints read back per pass: vertex offsets (S+1), face offsets (S+1), counters
+  // (MS_INTS), tile counts (4: lite, all, band, redo), per-slot error bits / violations / redo
+  // flag (S each), the lite kernel's wait record (STD_INTS)
+  int* rb = nullptr;
+  int *offs_v = nullptr, *offs_f = nullptr, *stat = nullptr, *cnt = nullptr, *slot_err = nullptr,
+      *slot_viol = nullptr, *slot_redo = nullptr, *diag = nullptr;
+  hipEvent_t ev[4] = {};
+  std::vector<float> hcodes, hv;
+  std::vector<int> hrb, hf;
+};
+
+static void mesh_batch_free(MeshBatch* b) {
+  if (!b) return;
+  for (hipEvent_t e : b->ev)
+    if (e) hipEventDestroy(e);
+  delete b;
+}
 
 struct dsr_mesher {
   dsr_ctx* ctx = nullptr;
@@ -2909,26 +2929,6 @@ static void mc_scan(hipStream_t s, const int* in, int n, int* out, int* bsum, in
   hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(MC_SCAN_BLOCK), 0, s, in, n, (const int*)bsum, out);
 }
 
-static int mc_run(dsr_mesher* m, float level, float* verts, int vcap, int* faces, int fcap, int* n_verts,
-                  int* n_faces);
-
-int dsr_mesher_run(dsr_mesher* m, const float* code, float level, float* verts, int vcap, int* faces,
-                   int fcap, int* n_verts, int* n_faces) {
-  if (!m || !code || !n_verts || !n_faces) return fail(m ? m->ctx : nullptr, "null argument");
-  dsr_ctx* ctx = m->ctx;
-  if (int rc = decoder_ready(ctx, m->dec)) return rc;
-  hipSetDevice(ctx->device);
-  hipStream_t s = ctx->stream;
-  const DevDecoder& D = m->dec->D;
-  float zc[CODE] = {};                               // a 32-D code runs padded with zeros
-  std::memcpy(zc, code, sizeof(float) * m->dec->code_len);
-  DSR_CHECK(ctx, hipMemcpyAsync(m->code, zc, sizeof(float) * CODE, hipMemcpyHostToDevice, s));
-  DSR_CHECK(ctx, hipStreamSynchronize(s));          // (zc is on this stack frame)
-  fold_codes(s, D, m->code, 1, m->b0, m->b4);
-  launch_fwd(s, std::min(ctx->n_cu, m->nt), D, {m->tiles, m->ntiles, m->desc, m->pts, m->b0, m->b4, m->vol});
-  return mc_run(m, level, verts, vcap, faces, fcap, n_verts, n_faces);
-}
-
 // Marching cubes over m->vol (already on m's context stream) and the copy-out.
 static int mc_run(dsr_mesher* m, float level, float* verts, int vcap, int* faces, int fcap, int* n_verts,
                   int* n_faces) {
@@ -2959,6 +2959,23 @@ static int mc_run(dsr_mesher* m, float level, float* verts, int vcap, int* faces
   return 0;
 }
 
+int dsr_mesher_run(dsr_mesher* m, const float* code, float level, float* verts, int vcap, int* faces,
+                   int fcap, int* n_verts, int* n_faces) {
+  if (!m || !code || !n_verts || !n_faces) return fail(m ? m->ctx : nullptr, "null argument");
+  dsr_ctx* ctx = m->ctx;
+  if (int rc = decoder_ready(ctx, m->dec)) return rc;
+  hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  const DevDecoder& D = m->dec->D;
+  float zc[CODE] = {};                               // a 32-D code runs padded with zeros
+  std::memcpy(zc, code, sizeof(float) * m->dec->code_len);
+  DSR_CHECK(ctx, hipMemcpyAsync(m->code, zc, sizeof(float) * CODE, hipMemcpyHostToDevice, s));
+  DSR_CHECK(ctx, hipStreamSynchronize(s));          // (zc is on this stack frame)
+  fold_codes(s, D, m->code, 1, m->b0, m->b4);
+  launch_fwd(s, std::min(ctx->n_cu, m->nt), D, {m->tiles, m->ntiles, m->desc, m->pts, m->b0, m->b4, m->vol});
+  return mc_run(m, level, verts, vcap, faces, fcap, n_verts, n_faces);
+}
+
 int dsr_mc_volume(dsr_ctx* ctx, const float* vol, int vol_dim, float level, float* verts, int vcap, int* faces,
                   int fcap, int* n_verts, int* n_faces) {
   if (!ctx || !vol || !n_verts || !n_faces) return fail(ctx, "null argument");
@@ -2981,45 +2998,6 @@ int dsr_mc_volume(dsr_ctx* ctx, const float* vol, int vol_dim, float level, floa
 // ------------------------------------------------------------------------------------
 // batched mesh extraction (dsr_mesh.hpp)
 // ------------------------------------------------------------------------------------
-// S slots of everything a mesh needs; a call runs its codes in passes of up to S.  S grows with
-// the calls' code counts up to MESH_MAX_SLOTS and while one pass's buffers stay within
-// MESH_BUDGET (the marching-cubes buffers hold the worst case of every slot: ~270 MB per slot at
-// 128^3, so 6 slots there; 16 up to 96^3).
-static constexpr int MESH_MAX_SLOTS = 16;
-static constexpr size_t MESH_BUDGET = (size_t)2 << 30;
-static constexpr float MESH_MARGIN = 0.01f;      // §3.4's first-iteration margin
-
-struct MeshBatch {
-  int S = 0, np = 0, ntl = 0, n_rb = 0;
-  int last_ns = 0;             // slots of the last pass (dsr_mesher_peek)
-  bool last_sign = false;
-  DevArena mem;
-  float4* pts = nullptr;       // the grid, once per slot (the kernels index it by ObjDesc.cand_off)
-  float *lite = nullptr, *vol = nullptr, *codes = nullptr, *b0 = nullptr, *b4 = nullptr, *verts = nullptr;
-  unsigned char *refine = nullptr, *tflag = nullptr;
-  int *flag = nullptr, *vidx = nullptr, *ntri = nullptr, *toff = nullptr, *bsum = nullptr, *faces = nullptr;
-  int *tmark = nullptr, *tpos = nullptr;
-  Tile *ltiles = nullptr, *atiles = nullptr, *etiles = nullptr, *rtiles = nullptr;
-  ObjDesc* desc = nullptr;
-  ObjState* st = nullptr;
-  // one record of ints read back per pass: vertex offsets (S+1), face offsets (S+1), counters
-  // (MS_INTS), tile counts (4: lite, all, band, redo), per-slot error bits / violations / redo
-  // flag (S each), the lite kernel's wait record (STD_INTS)
-  int* rb = nullptr;
-  int *offs_v = nullptr, *offs_f = nullptr, *stat = nullptr, *cnt = nullptr, *slot_err = nullptr,
-      *slot_viol = nullptr, *slot_redo = nullptr, *diag = nullptr;
-  hipEvent_t ev[4] = {};
-  std::vector<float> hcodes, hv;
-  std::vector<int> hrb, hf;
-};
-
-static void mesh_batch_free(MeshBatch* b) {
-  if (!b) return;
-  for (hipEvent_t e : b->ev)
-    if (e) hipEventDestroy(e);
-  delete b;
-}
-
 static size_t mesh_slot_bytes(const dsr_mesher* m) {
   const size_t n = m->n, nc = (size_t)(m->d - 1) * (m->d - 1) * (m->d - 1), np = (n + LTILE - 1) / LTILE * LTILE;
   return np * (sizeof(float4) + 2 * sizeof(float) + 1) + sizeof(int) * std::max(3 * n, np) + sizeof(int) * 3 * n +
@@ -4020,6 +3998,9 @@ int dsr_scene_peek(dsr_scene* sc, int obj, int cap, int* idx, float* x_obj, floa
   return 0;
 }
 
+// ------------------------------------------------------------------------------------
+// raw decoder queries (dsr_sdf_eval)
+// ------------------------------------------------------------------------------------
 int dsr_sdf_eval(dsr_ctx* ctx, const dsr_decoder* dec, const float* code, const float* pts, int n,
                  float* sdf, float* jac) {
   if (!ctx || !dec || !code || (n > 0 && (!pts || !sdf))) return fail(ctx, "null argument");

@@ -147,21 +147,12 @@ struct Tile {
 
 // Early ray termination (k_sample_pass): the fwd kernels flag a ray dead once one of its
 // samples decodes to sdf <= -cut_off (occupancy exactly 1, transmittance exactly 0 after it).
-// dead-flag accesses (experiment DSR_EXP_DEADWT: system-scope relaxed atomics, i.e. vector
-// loads / stores that bypass the non-coherent caches)
+// dead-flag accesses
 __device__ __forceinline__ void dead_put(int* p, int v) {
-#ifdef DSR_EXP_DEADWT
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
   *p = v;
-#endif
 }
 __device__ __forceinline__ int dead_get(int* p) {
-#ifdef DSR_EXP_DEADWT
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
   return *p;
-#endif
 }
 #ifdef DSR_EXP_PROV
 // Diagnostic build only (tools/prov_diff.py): per-run provenance of the early

@@ -62,8 +62,8 @@ struct FwdQuery {
   FwdKernel kernel = nullptr;                          // null: the query's exact kernel (query_fwd_variant)
 };
 static void launch_fwd(hipStream_t s, int grid, const DevDecoder& D, const FwdQuery& q) {
-  hipLaunchKernelGGL(q.kernel ? q.kernel : fwd_kernel_for(D, query_fwd_variant()), dim3(grid), dim3(512), 0, s, D,
-                     q.tiles, q.n_tiles, q.desc, q.pts, q.b0, q.b4, q.out, (unsigned*)nullptr, q.ert, q.mask);
+  hipLaunchKernelGGL(q.kernel ? q.kernel : fwd_kernel_for(D, query_fwd_variant()).kernel, dim3(grid), dim3(512), 0, s,
+                     D, q.tiles, q.n_tiles, q.desc, q.pts, q.b0, q.b4, q.out, (unsigned*)nullptr, q.ert, q.mask);
 }
 // the lite pass over the same head; q.ert carries its settings
 static void launch_lite(hipStream_t s, int grid, const DevDecoder& D, const FwdQuery& q) {
@@ -88,9 +88,9 @@ struct JacQuery {
   float* lnw = nullptr;                  // LayerNorm decoders: decoder_ready's workspace
 };
 static void launch_jac(hipStream_t s, int grid, const DevDecoder& D, const JacQuery& q) {
-  hipLaunchKernelGGL(jac_kernel_for(D), dim3(grid), dim3(512), 0, s, D, q.tiles, q.n_tiles, q.desc, q.st, q.surf_pts,
-                     q.render_pts, q.render_res, q.b0, q.b4, q.P, q.slots, q.query_pts, q.raw_out, q.res_out, q.mask,
-                     q.lnw);
+  hipLaunchKernelGGL(jac_kernel_for(D).kernel, dim3(grid), dim3(512), 0, s, D, q.tiles, q.n_tiles, q.desc, q.st,
+                     q.surf_pts, q.render_pts, q.render_res, q.b0, q.b4, q.P, q.slots, q.query_pts, q.raw_out, q.res_out,
+                     q.mask, q.lnw);
 }
 
 // an integer test hook (read under DSR_TEST_HOOKS=1 only): the default outside [lo, hi]

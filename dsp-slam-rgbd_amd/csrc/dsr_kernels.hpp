@@ -1559,13 +1559,7 @@ struct Jac16Shared {
 // (tools/bias_probe.py: J bias 3.4e-8 -> 2.3e-8 of |J|, random 8.3e-7 -> 5.8e-7; fp32 numpy
 // 5.7e-9 / 7.2e-7) — the sum b = sum_p J_p r_p cancels to ~1e-5 of its terms on a converging
 // object, so that bias, not the random error, is what its pose rows see.
-#if defined(DSR_EXP_NOLS)
-constexpr int BWD_LS = 0;
-#elif defined(DSR_EXP_BLS1)
-constexpr int BWD_LS = 1;
-#else
 constexpr int BWD_LS = 2;
-#endif
 
 // NB: A ring depth of the split GEMMs (gemm16_sel; 0 = the two-set gemm16_tile).  Lane-derived
 // values are re-derived per layer from an opaque lane id (dsr_mlp_lite.hpp, "Register
@@ -2074,25 +2068,6 @@ __device__ inline float rotation_prior(const float* Tco, float* jrot) {
   jrot[5] = (float)(-(r3[0 * 3 + 2] * r3[2 * 3 + 1] - r3[0 * 3 + 1] * r3[2 * 3 + 2]) / dr);  // -R_oc[0][1]
   return (float)res_rot;
 }
-#ifdef DSR_EXP_PRIOR_FP32
-// Experiment build only: the reference's own fp32 chain (det -> pow(1/3) -> divide -> inverse),
-// round 3's code — DESIGN.md §5 (late round 4) used it to rule the fp64 prior out as the cause
-// of kitti5's iteration-1 offset.
-__device__ inline float rotation_prior_fp32(const float* Tco, float* jrot) {
-  float rco[16], rf[9], roc[9];
-  for (int i = 0; i < 16; ++i) rco[i] = Tco[i];
-  const float sc = powf(det3(rco), 0.33333334f);
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) rf[i * 3 + j] = rco[i * 4 + j] / sc;
-  inv_small<3>(rf, roc);
-  const float res_rot = 1.f - (-rf[1 * 3 + 1]);
-  for (int i = 0; i < NPOSE; ++i) jrot[i] = 0.f;
-  if (res_rot < 1e-7f) return 0.f;
-  jrot[3] = roc[2 * 3 + 1];
-  jrot[5] = -roc[0 * 3 + 1];
-  return res_rot;
-}
-#endif
 
 // Several views of one object (dsr_reconstruct_views): every view is an ordinary batch member
 // (own ObjDesc / ObjState, own samples, tiles and red[] sums) and the members of one object are
@@ -2224,11 +2199,7 @@ __device__ __forceinline__ void solve_object(const int o, const int nm, const Ob
   // rotation prior, loss.py:169-192, at the current (pre-update) pose (rotation_prior), by a
   // lane of wave 1 while the loads land (its result is only read when no failure exit is taken)
   if (tid == 64) {
-#ifdef DSR_EXP_PRIOR_FP32
-    scal[1] = rotation_prior_fp32(S.Tco, jrot);
-#else
     scal[1] = rotation_prior(S.Tco, jrot);
-#endif
   }
   __syncthreads();
   const int it = S.iters_done;

@@ -42,12 +42,8 @@ constexpr int PH = 528;                      // LDS pitch of the fp16 images (ha
 // accumulators hold -(W h), their rounding leans the other way, and the epilogues multiply them
 // back by row_sign(q) (exact) — half the rows lean up, half down, and no scale survives.  Zero
 // cost: the sign rides on the epilogue's existing unscale multiply.  The lite pass reads its own
-// unsigned fp16 copy (Wl_raw); a DSR_EXP_NOSIGN build (A/B) packs without signs.
-#ifdef DSR_EXP_NOSIGN
-constexpr bool SPLIT_ROW_SIGNS = false;
-#else
+// unsigned fp16 copy (Wl_raw).
 constexpr bool SPLIT_ROW_SIGNS = true;
-#endif
 // the sign of 16-row block q (rows 64w + 16q .. +15) of a packed split matrix; for lin0^T's
 // 80-row pack, whose wave w owns rows 16w .. 16w + 15, pass w
 __device__ __forceinline__ constexpr float row_sign(int q) { return (SPLIT_ROW_SIGNS && (q & 1)) ? -1.f : 1.f; }
@@ -57,13 +53,8 @@ __device__ __forceinline__ constexpr float row_sign(int q) { return (SPLIT_ROW_S
 // sign as well (odd 16-point blocks negated: a checkerboard, measured in round 5) cancelled that
 // lean over points, but made a point's result depend on its slot in the tile — the lite pass's
 // band re-decode, a re-run from a saved state and an 8-rank shard then disagreed with the exact
-// pass in the last bits (test_gpu_parity.py's bitwise checks) — so it is not built;
-// DSR_EXP_COLSIGN (A/B) restores it.
-#ifdef DSR_EXP_COLSIGN
-__device__ __forceinline__ constexpr float col_sign(int cb) { return (SPLIT_ROW_SIGNS && (cb & 1)) ? -1.f : 1.f; }
-#else
+// pass in the last bits (test_gpu_parity.py's bitwise checks) — so it is not built.
 __device__ __forceinline__ constexpr float col_sign(int) { return 1.f; }
-#endif
 __device__ __forceinline__ constexpr float rc_sign(int q, int cb) { return row_sign(q) * col_sign(cb); }
 
 struct Fwd16Shared {
@@ -283,9 +274,6 @@ __device__ __forceinline__ void gemm16_ring(const _Float16* Wl, int w, const _Fl
   const _Float16* Bh = Hh + boff;
   const _Float16* Bl = Hl + boff;
   auto lda = [&](int q, int t, int piece) {
-#ifdef DSR_EXP_NOSTREAM            // timing experiment (invalid results): A from one k step only
-    t = 0;
-#endif
     return __builtin_bit_cast(
         half8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, ((q * T + t) * 2 + piece) * 1024, 0));
   };
@@ -340,10 +328,8 @@ __device__ __forceinline__ void gemm16_ring(const _Float16* Wl, int w, const _Fl
           continue;
         }
         if constexpr (LS == 1) continue;         // below, the block's four q at once
-#ifndef DSR_EXP_ONEPROD            // timing experiment (invalid results): the hi.hi product only
         x = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[j][q], bh[cb & 1], x, 0, 0, 0);
         x = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j][q], bl[cb & 1], x, 0, 0, 0);
-#endif
         acc[q][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j][q], bh[cb & 1], x, 0, 0, 0);
       }
       if constexpr (LS == 1) {
@@ -403,23 +389,10 @@ __device__ __forceinline__ void gemm16_sel(const _Float16* Wl, int w, int T, con
 // the same bits whichever kernel computes them (test_gpu_parity.py: the lite pass against the
 // exact decode, the broken-block fallback, the surface forward of small batches;
 // test_gpu_bench.py: 8-rank shards against one rank).
-#if defined(DSR_EXP_JFLS0)
-constexpr int JFWD_LS = 0;
-#elif defined(DSR_EXP_JFLS1)
-constexpr int JFWD_LS = 1;
-#else
 constexpr int JFWD_LS = 2;
-#endif
-// the exact pass's surface tiles run the Jacobian kernel's forward chain (the same one unless an
-// A/B build sets them apart)
+// the exact pass's surface tiles run the Jacobian kernel's forward chain
 constexpr int SURF_LS = JFWD_LS;
-#if defined(DSR_EXP_FLS0)
-constexpr int FWD_LS = 0;
-#elif defined(DSR_EXP_FLS1)
-constexpr int FWD_LS = 1;
-#else
 constexpr int FWD_LS = 2;
-#endif
 
 // power-of-two scale exponent s such that m * 2^s < 2^14 (m >= 0); 0 for m == 0 / non-finite
 __device__ __forceinline__ int act_scale_exp(float m) {

@@ -5,8 +5,12 @@ Usage (GPU box): DSR_LIB=<path to libdsr.so> python tools/batch_sig.py out.npz
                  python tools/batch_sig.py --compare a.npz b.npz
 A layout-only change (LDS swizzles, schedules) or a host-side refactor must leave every array
 bitwise equal.  The batch arrays (rec, cnt) and the 5000-point query (y, j) are signed on the
-default decoder; the small queries below on it ("def") and on a LayerNorm decoder ("ln", the
-Jacobian kernel's workspace path), at the smallest shapes that take every host path:
+default decoder, and so are the two other creation paths at their smallest shapes, 2 iterations each:
+  cap_1 / cap_2   a 2-slot capacity batch (dsr_batch_create_capacity: 70 points, 270 rays per slot)
+                  refilled with one object and run, then with two and run again
+  tied            dsr_reconstruct_views, 2 objects x 2 views at 70 points (a tied batch)
+The small queries below run on it ("def") and on a LayerNorm decoder ("ln", the Jacobian kernel's
+workspace path), at the smallest shapes that take every host path:
   sdf / jac     dsr_sdf_eval with the Jacobian, 70 points (two 64-point tiles, one partial)
   pose          dsr_pose_only_batch, 2 objects x 70 points, 6 iterations (the iteration-4 filter)
   mesh1_* / meshb_*   dsr_mesher_run / dsr_mesher_run_batch, 8^3 grid, 2 codes
@@ -52,13 +56,55 @@ ctx.check(lib.dsr_batch_run(batch), "run")
 ctx.check(lib.dsr_batch_download(batch, outs), "dl")
 st = L.Stats()
 ctx.check(lib.dsr_batch_stats(batch, C.byref(st)), "stats")
-rec = np.array([list(o.t_cam_obj) + list(o.code) + [o.loss, o.is_good, o.iters_done] for o in outs], np.float32)
+
+
+def records(outs):
+    return np.array([list(o.t_cam_obj) + list(o.code) + [o.loss, o.is_good, o.iters_done] for o in outs], np.float32)
+
+
+rec = records(outs)
 cnt = np.array([st.fwd_points, st.refine_points, st.jac_points], np.int64)
 rng = np.random.default_rng(0)
 z = (0.3 * rng.standard_normal(64)).astype(np.float32)
 x = rng.uniform(-0.9, 0.9, (5000, 3)).astype(np.float32)
 y, j = sdf_eval(dec, z, x, with_jac=True)
 sig = dict(rec=rec, cnt=cnt, y=y, j=j)
+
+
+def creation_paths(d):
+    """The capacity and the tied creation path on decoder ``d``: {name: out-records}."""
+    optim = dict(S.KITTI_OPTIM, joint_optim=dict(S.KITTI_OPTIM["joint_optim"], num_iterations=2))
+    opt = Optimizer(d, ForceKeyErrorDict(data_type="KITTI", optimizer=optim))
+    objs = [S.kitti_object(30 + i, n_pts=70) for i in range(2)]       # 70 points, 70 + 200 rays
+    keep = []
+    ins = (L.ObjectIn * 2)()
+    for i, ob in enumerate(objs):
+        ins[i] = opt._object_in(ob.t_cam_obj, ob.pts, ob.rays, ob.depth, None, keep)
+    out = {}
+    h = C.c_void_p()
+    ctx.check(lib.dsr_batch_create_capacity(ctx.handle, d.handle, C.byref(opt.params), 2, 70, 270, 0, C.byref(h)),
+              "create_capacity")
+    try:
+        for fill in (1, 2):
+            o = (L.ObjectOut * fill)()
+            ctx.check(lib.dsr_batch_refill(h, fill, ins), "refill")
+            ctx.check(lib.dsr_batch_run(h), "run")
+            ctx.check(lib.dsr_batch_download(h, o), "dl")
+            out["cap_%d" % fill] = records(o)
+            assert all(x.is_good and x.iters_done == 2 for x in o), "capacity batch: an object failed early"
+    finally:
+        lib.dsr_batch_destroy(h)
+    views = [S.make_object_views(40 + i, n_views=2, n_pts=70) for i in range(2)]
+    res = opt.reconstruct_objects_views([(v.t_cam_obj, v.views, None) for v in views])
+    assert all(r["is_good"] and r["fail_view"] == -1 and r["iters_done"] == 2 for r in res), "tied batch: a view failed"
+    zero = np.zeros(16, np.float32)                  # (a failed object's result has no pose and no code)
+    out["tied"] = np.array([list(zero if r["t_cam_obj"] is None else r["t_cam_obj"].reshape(-1)) +
+                            list(np.tile(zero, 4) if r["code"] is None else r["code"]) +
+                            [r["loss"], r["is_good"], r["iters_done"], r["fail_view"]] for r in res], np.float32)
+    return out
+
+
+sig.update(creation_paths(dec))
 
 
 def pose(tx, tz, s=1.0):
