@@ -27,6 +27,7 @@
 #include "dsr_render.hpp"
 #include "dsr_scene.hpp"
 #include "dsr_frame.hpp"
+#include "dsr_lidar.hpp"
 
 #ifndef DSR_DEFAULT_FWD_VARIANT
 #define DSR_DEFAULT_FWD_VARIANT 12  // split-fp16 (3xFP16) + s_setprio (A/B: tools/fwd_variants.py)
@@ -359,6 +360,14 @@ struct dsr_batch {
   // the last fill was dsr_batch_refill_frame_poses with this max_pts (§3.5c; its keep flags and pose
   // records follow the ingest's part of frame_dev), else -1
   int frame_pose_pts = -1;
+  // Sweep refills (dsr_batch_refill_lidar): one pinned block (sweep | instance | masks | prepared
+  // detections) and one device block (the same, then the kernels' tables and records;
+  // dsr_lidar.hpp), grown to the largest sweep and image seen and freed with the batch.
+  // lidar_shape.n_det: detections of the last fill if it was a sweep, else -1.
+  void* lidar_host = nullptr;
+  void* lidar_dev = nullptr;
+  size_t lidar_host_bytes = 0, lidar_dev_bytes = 0;
+  LidarShape lidar_shape{0, 3, 0, 0, -1};
 };
 
 #define DSR_CHECK(ctx, call)                                                        \
@@ -1232,6 +1241,8 @@ int dsr_batch_destroy(dsr_batch* b) {
     if (sg.host) hipHostFree(sg.host);
   if (b->frame_host) hipHostFree(b->frame_host);
   if (b->frame_dev) hipFree(b->frame_dev);
+  if (b->lidar_host) hipHostFree(b->lidar_host);
+  if (b->lidar_dev) hipFree(b->lidar_dev);
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (b->up_ev) ctx->ev_plain.push_back(b->up_ev);
   for (auto& e : b->ev)
@@ -1727,6 +1738,7 @@ int dsr_batch_refill(dsr_batch* b, int n_obj, const dsr_object_in* in) {
   b->n_active = n_obj;
   b->frame_n = -1;
   b->frame_pose_pts = -1;
+  b->lidar_shape.n_det = -1;
   b->ran = false;
   return 0;
 }
@@ -1921,6 +1933,7 @@ static int batch_refill_frame_impl(dsr_batch* b, const dsr_camera* cam, const ds
   b->frame_w = W;
   b->frame_h = H;
   b->frame_pose_pts = pose_params ? params->max_pts : -1;
+  b->lidar_shape.n_det = -1;
   b->ran = false;
   return 0;
 }
@@ -2800,6 +2813,180 @@ int dsr_reconstruct_views(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_
   if (!rc && stats) rc = dsr_batch_stats(b, stats);
   dsr_batch_destroy(b);
   return rc;
+}
+
+// ---- LiDAR keyframe ingest (include/dsr.h; kernels and the host rule in dsr_lidar.hpp)
+int dsr_lidar_params_default(dsr_lidar_params* p) {
+  if (!p) return -2;
+  p->max_pts = 250;
+  p->max_bg = 200;
+  p->downsample = 4;
+  p->expand = 5;
+  p->min_mask_area = 1000;
+  p->radius = 3.0f;
+  p->box_margin = 1.1f;
+  return 0;
+}
+
+// t_cam_velo is validated as dsr_reconstruct_views validates t_view_ref
+static bool lidar_rigid(const float* t) {
+  float inv[16];
+  return t && rigid_inverse(t, inv);
+}
+
+static LidarShape lidar_shape(const dsr_camera* cam, int n_velo, int stride, int n_det) {
+  return LidarShape{n_velo, stride, cam->width, cam->height, n_det};
+}
+
+int dsr_lidar_inputs_host(const dsr_camera* cam, const dsr_lidar_params* params, const float* t_cam_velo,
+                          const float* velo, int n_velo, int stride, const int* instance, int n_masks,
+                          const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
+                          float* rays, float* dobs, dsr_lidar_det_out* out) {
+  if (lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks, masks, n_det, dets))
+    return -2;
+  lidar_inputs_host_impl(frame_cam(cam), *params, t_cam_velo, velo, n_velo, stride, instance, n_masks, masks, n_det,
+                         dets, pts, rays, dobs, out);
+  return 0;
+}
+
+int dsr_lidar_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_lidar_params* params,
+                     const float* t_cam_velo, const float* velo, int n_velo, int stride, const int* instance,
+                     int n_masks, const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
+                     float* rays, float* dobs, dsr_lidar_det_out* out) {
+  if (!ctx) return -2;
+  if (const char* m = lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks,
+                                       masks, n_det, dets))
+    return fail(ctx, m);
+  if (n_det > 0 && (!pts || !rays || !dobs || !out)) return fail(ctx, "lidar: null output arrays");
+  if (n_det == 0) return 0;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const LidarShape S = lidar_shape(cam, n_velo, stride, n_det);
+  const size_t up = lidar_upload_bytes(S), all = lidar_dev_bytes(S);
+  const size_t np = (size_t)n_det * params->max_pts * 3, nr = (size_t)n_det * ((size_t)params->max_pts + params->max_bg) * 3,
+               nz = (size_t)n_det * params->max_pts;
+  std::vector<char> host(up);
+  lidar_pack(host.data(), S, *params, t_cam_velo, velo, instance, n_masks, masks, dets);
+  char* dev = nullptr;
+  float* o = nullptr;                            // pts | rays | dobs
+  hipStream_t s = ctx->stream;
+  int rc = 0;
+  auto chk = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == 0) {
+      ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+      rc = -1;
+    }
+    return e == hipSuccess;
+  };
+  if (chk(hipMalloc((void**)&dev, all), "hipMalloc (lidar)") &&
+      chk(hipMalloc((void**)&o, sizeof(float) * (np + nr + nz)), "hipMalloc (lidar outputs)")) {
+    const LidarDev D = lidar_carve(dev, S);
+    // rows beyond a detection's counts come back as the caller had them
+    chk(hipMemcpyAsync(dev, host.data(), up, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o, pts, sizeof(float) * np, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o + np, rays, sizeof(float) * nr, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    chk(hipMemcpyAsync(o + np + nr, dobs, sizeof(float) * nz, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+    if (rc == 0) {
+      lidar_launch(s, frame_cam(cam), *params, lidar_xf(t_cam_velo), S, n_masks, D, nullptr, o, o + np, o + np + nr);
+      chk(hipGetLastError(), "lidar kernels");
+      chk(hipMemcpyAsync(pts, o, sizeof(float) * np, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(rays, o + np, sizeof(float) * nr, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(dobs, o + np + nr, sizeof(float) * nz, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+      chk(hipMemcpyAsync(out, D.recs, sizeof(dsr_lidar_det_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+    }
+    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
+  }
+  if (o) hipFree(o);
+  if (dev) hipFree(dev);
+  return rc;
+}
+
+int dsr_batch_refill_lidar(dsr_batch* b, const dsr_camera* cam, const dsr_lidar_params* params,
+                           const float* t_cam_velo, const float* velo, int n_velo, int stride,
+                           const int* instance, int n_masks, const dsr_lidar_mask* masks, int n_det,
+                           const dsr_lidar_det* dets) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  if (!b->capacity) return fail(ctx, "dsr_batch_refill_lidar needs a batch from dsr_batch_create_capacity");
+  if (const char* m = lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks,
+                                       masks, n_det, dets))
+    return fail(ctx, m);
+  if (n_det > b->n_obj) return fail(ctx, "refill_lidar: n_det exceeds the batch's object capacity");
+  if (params->max_pts > b->max_pts) return fail(ctx, "refill_lidar: max_pts exceeds the batch's max_pts");
+  if ((long long)params->max_pts + params->max_bg > b->max_rays)
+    return fail(ctx, "refill_lidar: max_pts + max_bg exceeds the batch's max_rays");
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  // the previous refill's copies read the staging buffers until they complete
+  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+  const LidarShape S = lidar_shape(cam, n_velo, stride, n_det);
+  const size_t up = lidar_upload_bytes(S), all = lidar_dev_bytes(S);
+  hipStream_t s = ctx->stream;
+  if (up > b->lidar_host_bytes) {
+    if (b->lidar_host) hipHostFree(b->lidar_host);
+    b->lidar_host = nullptr;
+    b->lidar_host_bytes = 0;
+    DSR_CHECK(ctx, hipHostMalloc(&b->lidar_host, up, hipHostMallocDefault));
+    b->lidar_host_bytes = up;
+  }
+  if (all > b->lidar_dev_bytes) {
+    // the kernels of an earlier sweep refill may still read the old block
+    DSR_CHECK(ctx, hipStreamSynchronize(s));
+    if (b->lidar_dev) hipFree(b->lidar_dev);
+    b->lidar_dev = nullptr;
+    b->lidar_dev_bytes = 0;
+    DSR_CHECK(ctx, hipMalloc(&b->lidar_dev, all));
+    b->lidar_dev_bytes = all;
+  }
+  lidar_pack(b->lidar_host, S, *params, t_cam_velo, velo, instance, n_masks, masks, dets);
+  const LidarDev Hd = lidar_carve(b->lidar_host, S);
+  auto* desc = static_cast<ObjDesc*>(b->stage[0].host);
+  auto* t_in = static_cast<float*>(b->stage[1].host);
+  auto* z_in = static_cast<float*>(b->stage[2].host);
+  auto* is_oc = static_cast<int*>(b->stage[3].host);
+  for (int o = 0; o < b->n_obj; ++o) {
+    ObjDesc d = b->hdesc[o];                       // the slot's offsets; k_lidar_bg_scan writes the counts
+    d.n_pts = d.n_rays = d.n_fg = 0;
+    desc[o] = d;
+    const dsr_lidar_det* x = o < n_det ? &dets[o] : nullptr;
+    float* t = t_in + (size_t)o * 16;
+    for (int i = 0; i < 16; ++i) t[i] = x ? Hd.dets[o].tco[i] : (i % 5 == 0 ? 1.f : 0.f);
+    float* z = z_in + (size_t)o * CODE;
+    std::memset(z, 0, sizeof(float) * CODE);
+    if (x && x->code) std::memcpy(z, x->code, sizeof(float) * b->dec->code_len);
+    is_oc[o] = 0;
+  }
+  for (int k = 0; k < 4; ++k)                      // desc, t_in, z_in, is_oc (pts / rays / dobs: the kernels)
+    DSR_CHECK(ctx, hipMemcpyAsync(b->stage[k].dev, b->stage[k].host, b->stage[k].bytes, hipMemcpyHostToDevice, s));
+  DSR_CHECK(ctx, hipMemcpyAsync(b->lidar_dev, b->lidar_host, up, hipMemcpyHostToDevice, s));
+  if (n_det > 0) {
+    lidar_launch(s, frame_cam(cam), *params, lidar_xf(t_cam_velo), S, n_masks, lidar_carve(b->lidar_dev, S), b->desc,
+                 b->pts, b->rays, b->dobs);
+    DSR_CHECK(ctx, hipGetLastError());
+  }
+  if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
+  DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
+  b->n_active = n_det;
+  b->frame_n = -1;
+  b->frame_pose_pts = -1;
+  b->lidar_shape = S;
+  b->ran = false;
+  return 0;
+}
+
+int dsr_batch_lidar_info(dsr_batch* b, dsr_lidar_det_out* out) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  if (b->lidar_shape.n_det < 0)
+    return fail(ctx, "dsr_batch_lidar_info: the batch's last fill was not a sweep (dsr_batch_refill_lidar)");
+  if (b->lidar_shape.n_det == 0) return 0;
+  if (!out) return fail(ctx, "null argument");
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+  const LidarDev D = lidar_carve(b->lidar_dev, b->lidar_shape);
+  DSR_CHECK(ctx, hipMemcpy(out, D.recs, sizeof(dsr_lidar_det_out) * b->lidar_shape.n_det, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------

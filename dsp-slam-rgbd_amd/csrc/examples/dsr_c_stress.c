@@ -5,7 +5,9 @@
  *
  *   dsr_c_stress               no-device paths: ABI version, argument validation and error
  *                              reporting of every entry point that checks its arguments before
- *                              touching the device, context creation (-3 without a device)
+ *                              touching the device, the host rules (dsr_scene_bin_host,
+ *                              dsr_lidar_inputs_host) on hand-computed inputs, context creation
+ *                              (-3 without a device)
  *   dsr_c_stress <dir>         the same inputs as dsr_c_smoke (weights.f32, params.f32,
  *                              objects.bin), then every device entry point with cross-checks:
  *                              one-shot batch twice (bitwise), resident batch create / run /
@@ -16,7 +18,9 @@
  *                              mesher (and dsr_mc_volume on its decoded grid) with ample and
  *                              with too small capacities, the batch call (dsr_mesher_run_batch:
  *                              ample and too small totals, n = 0) against it, scene queries
- *                              (dsr_scene_*) against sdf_eval and their records, forced audit
+ *                              (dsr_scene_*) against sdf_eval and their records, the LiDAR
+ *                              ingest (dsr_lidar_inputs against a hand-computed sweep and the
+ *                              host rule, dsr_batch_refill_lidar against dsr_batch_refill), forced audit
  *                              violations and their spare-iteration redo (test hooks), and the
  *                              error paths of a live context.  Exit status 0 = every check held.
  */
@@ -66,6 +70,149 @@ static const dsr_decoder_desc DESC = {64, 9, {512, 512, 512, 445, 512, 512, 512,
 
 static int same_out(const dsr_object_out* a, const dsr_object_out* b, int n) {
   return memcmp(a, b, sizeof(dsr_object_out) * (size_t)n) == 0;
+}
+
+/* A ten-point sweep around one box whose outcome is computed by hand.  theta = 0
+ * and t_cam_velo an axis permutation keep every value exact: box axes x_0 = p_x - 8, x_1 = p_z,
+ * x_2 = -p_y with half extents (1.1, 1, 2.2), the cube (5, 11) x (-3, 3) x (-4, 2), camera point
+ * q = (-p_y, -p_z, p_x), pixel (16 + 16 q_x / q_z, 12 + 16 q_y / q_z). */
+typedef struct {
+  dsr_camera cam;
+  dsr_lidar_params par;
+  float tcv[16];
+  float velo[10][4];
+  int inst[24 * 32];
+  dsr_lidar_mask masks[2];
+  dsr_lidar_det det;
+} lidar_scene;
+
+static void lidar_scene_make(lidar_scene* s) {
+  const dsr_camera cam = {32, 24, 16.f, 16.f, 16.f, 12.f};
+  const float tcv[16] = {0, -1, 0, 0, 0, 0, -1, 0, 1, 0, 0, 0, 0, 0, 0, 1};
+  const float velo[10][4] = {{8.f, 0.f, 0.f, 0.1f},       /* in: candidate 0 -> row 0, pixel (16, 12) */
+                             {8.f, 1.f, 0.5f, 0.2f},      /* in: candidate 1, not picked */
+                             {8.f, -2.f, -0.5f, 0.3f},    /* in: candidate 2 -> row 1, pixel (20, 13) */
+                             {8.f, 2.5f, 0.f, 0.4f},      /* near; x_2 = -2.5 is outside */
+                             {9.f, 0.f, 0.5f, 0.5f},      /* in: candidate 3, not picked */
+                             {9.5f, 0.f, 0.f, 0.6f},      /* near; x_0 = 1.5 is outside */
+                             {8.f, 0.f, 1.f, 0.7f},       /* near; x_1 == e_1 is outside (strict) */
+                             {20.f, 0.f, 0.f, 0.8f},      /* not near */
+                             {8.f, 3.f, 0.f, 0.9f},       /* p_y == hi_y: not near (strict) */
+                             {7.5f, -1.f, -0.25f, 1.f}};  /* in: candidate 4 -> row 2, pixel (18, 12) */
+  s->cam = cam;
+  dsr_lidar_params_default(&s->par);
+  s->par.max_pts = 3;
+  s->par.min_mask_area = 100;
+  memcpy(s->tcv, tcv, sizeof tcv);
+  memcpy(s->velo, velo, sizeof velo);
+  for (int v = 0; v < 24; ++v)
+    for (int u = 0; u < 32; ++u) s->inst[v * 32 + u] = (u >= 10 && u <= 24 && v >= 8 && v <= 16) ? 7 : -1;   /* 135 pixels */
+  const dsr_lidar_mask masks[2] = {{9, {0, 0, -1, -1}}, {7, {0, 0, -1, -1}}};
+  memcpy(s->masks, masks, sizeof masks);
+  const dsr_lidar_det det = {{8.f, 0.f, -1.f}, {2.f, 4.f, 2.f}, 0.f, NULL};
+  s->det = det;
+}
+
+/* the hand-computed outcome: 8 near, 5 in, rows from candidates sel(i, 3, 5) = 0, 2, 4, all three
+ * projected onto label 7 (entry 1); its tight box (10, 8, 24, 16) grows to (5, 3, 29, 21), the 4 x 6
+ * grid has rows 3, 9, 15, 21 and columns 5, 9, 14, 19, 24, 29, of which 6 + 3 + 3 + 6 miss the mask */
+static void lidar_scene_check(const float* pts, const float* rays, const float* dobs, const dsr_lidar_det_out* o) {
+  CHECK(o->status == DSR_LIDAR_OK && o->n_near == 8 && o->n_crop == 5 && o->n_pts == 3, "lidar counts %d %d %d %d",
+        o->status, o->n_near, o->n_crop, o->n_pts);
+  CHECK(o->n_proj == 3 && o->mask == 1 && o->n_hits == 3 && o->n_mask_px == 135 && o->n_bg == 18,
+        "lidar association %d %d %d %d %d", o->n_proj, o->mask, o->n_hits, o->n_mask_px, o->n_bg);
+  CHECK(o->box[0] == 5 && o->box[1] == 3 && o->box[2] == 29 && o->box[3] == 21 && o->grid_h == 4 && o->grid_w == 6,
+        "lidar box %d %d %d %d grid %d x %d", o->box[0], o->box[1], o->box[2], o->box[3], o->grid_h, o->grid_w);
+  const float want[9] = {0.f, 0.f, 8.f, 2.f, 0.5f, 8.f, 1.f, 0.25f, 7.5f};
+  for (int i = 0; i < 9; ++i) CHECK(pts[i] == want[i], "lidar point value %d: %g", i, pts[i]);
+  CHECK(dobs[0] == 8.f && dobs[1] == 8.f && dobs[2] == 7.5f, "lidar depths");
+  CHECK(rays[0] == 0.f && rays[2] == 1.f && rays[3] == 0.25f && rays[4] == 0.0625f && rays[6] == 1.f / 7.5f,
+        "lidar foreground rays %g %g", rays[3], rays[6]);
+  CHECK(rays[9] == -0.6875f && rays[10] == -0.5625f && rays[11] == 1.f, "lidar first background ray %g %g", rays[9],
+        rays[10]);
+  CHECK(rays[3 * 20] == (29.f - 16.f) / 16.f && rays[3 * 20 + 1] == (21.f - 12.f) / 16.f, "lidar last background ray");
+  const float sg = 1.1f * 2.f;                      /* box_margin l / 2, exact */
+  CHECK(o->t_cam_obj[2] == sg && o->t_cam_obj[5] == -sg && o->t_cam_obj[8] == sg && o->t_cam_obj[11] == 8.f &&
+            o->t_cam_obj[0] == 0.f && o->t_cam_obj[3] == 0.f && o->t_cam_obj[7] == 0.f && o->t_cam_obj[15] == 1.f,
+        "lidar t_cam_obj %g %g %g %g", o->t_cam_obj[2], o->t_cam_obj[5], o->t_cam_obj[8], o->t_cam_obj[11]);
+}
+
+/* the LiDAR ingest without a device: its argument errors and the host rule on the scene above */
+static void lidar_no_device_paths(void) {
+  lidar_scene s;
+  lidar_scene_make(&s);
+  float pts[9], rays[3 * 203], dobs[3];
+  dsr_lidar_det_out o;
+#define LIDAR_HOST(cam_, par_, tcv_, velo_, n_, stride_, inst_, nm_, masks_, nd_, det_) \
+  dsr_lidar_inputs_host(cam_, par_, tcv_, velo_, n_, stride_, inst_, nm_, masks_, nd_, det_, pts, rays, dobs, &o)
+  for (int i = 0; i < 3 * 203; ++i) rays[i] = -7.f;
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, &s.det) == 0, "lidar_inputs_host failed");
+  lidar_scene_check(pts, rays, dobs, &o);
+  CHECK(rays[3 * 21] == -7.f, "lidar_inputs_host wrote beyond its rows");
+  CHECK(dsr_lidar_params_default(NULL) < 0, "lidar_params_default(NULL) accepted");
+  CHECK(s.par.max_bg == 200 && s.par.downsample == 4 && s.par.expand == 5 && s.par.radius == 3.f && s.par.box_margin == 1.1f,
+        "lidar defaults");
+  CHECK(LIDAR_HOST(NULL, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, &s.det) < 0, "lidar: NULL camera accepted");
+  CHECK(LIDAR_HOST(&s.cam, NULL, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, &s.det) < 0, "lidar: NULL params accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, NULL, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, &s.det) < 0, "lidar: NULL t_cam_velo accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, NULL, 10, 4, s.inst, 2, s.masks, 1, &s.det) < 0, "lidar: NULL sweep accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, NULL, 2, s.masks, 1, &s.det) < 0, "lidar: NULL image accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, NULL, 1, &s.det) < 0, "lidar: NULL masks accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, NULL) < 0, "lidar: NULL detections accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 2, s.inst, 2, s.masks, 1, &s.det) < 0, "lidar: stride 2 accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], -1, 4, s.inst, 2, s.masks, 1, &s.det) < 0, "lidar: n_velo -1 accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], (1 << 24) + 1, 4, s.inst, 2, s.masks, 1, &s.det) < 0,
+        "lidar: n_velo 2^24 + 1 accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, -1, s.masks, 1, &s.det) < 0, "lidar: n_masks -1 accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, DSR_LIDAR_MAX_MASKS + 1, s.masks, 1, &s.det) < 0,
+        "lidar: n_masks 257 accepted");
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, -1, &s.det) < 0, "lidar: n_det -1 accepted");
+  {
+    lidar_scene b = s;
+    b.tcv[1] = -1.1f;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: scaled t_cam_velo accepted");
+    b = s;
+    b.tcv[1] = 1.f;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: reflection accepted");
+    b = s;
+    b.tcv[15] = 2.f;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: last row accepted");
+    b = s;
+    b.det.theta = NAN;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: NaN theta accepted");
+    b = s;
+    b.det.trans[1] = INFINITY;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: inf trans accepted");
+    b = s;
+    b.det.size[2] = 0.f;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: size 0 accepted");
+    b = s;
+    b.par.radius = 0.f;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: radius 0 accepted");
+    b = s;
+    b.par.box_margin = INFINITY;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: inf box_margin accepted");
+    b = s;
+    b.par.max_pts = 0;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: max_pts 0 accepted");
+    b = s;
+    b.cam.fx = 0.f;
+    CHECK(LIDAR_HOST(&b.cam, &b.par, b.tcv, &b.velo[0][0], 10, 4, b.inst, 2, b.masks, 1, &b.det) < 0, "lidar: fx 0 accepted");
+  }
+  /* an empty sweep and an empty mask list are fine: NO_POINTS; the pose is still recorded */
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, NULL, 0, 4, s.inst, 0, NULL, 1, &s.det) == 0, "lidar: empty sweep refused");
+  CHECK(o.status == DSR_LIDAR_NO_POINTS && o.n_pts == 0 && o.mask == -1 && o.t_cam_obj[11] == 8.f, "lidar: empty sweep record");
+  /* the whole sweep against an empty mask list: NO_MATCH, rows written all the same */
+  pts[8] = -7.f;
+  CHECK(LIDAR_HOST(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 0, NULL, 1, &s.det) == 0, "lidar: no masks refused");
+  CHECK(o.status == DSR_LIDAR_NO_MATCH && o.n_pts == 3 && o.n_proj == 3 && o.n_hits == 0 && o.n_bg == 0 && pts[8] == 7.5f,
+        "lidar: no-mask record");
+#undef LIDAR_HOST
+  CHECK(dsr_lidar_inputs(NULL, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, &s.det, pts, rays, dobs, &o) < 0,
+        "lidar_inputs(NULL ctx) accepted");
+  CHECK(dsr_batch_refill_lidar(NULL, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, &s.det) < 0,
+        "refill_lidar(NULL) accepted");
+  CHECK(dsr_batch_lidar_info(NULL, &o) < 0, "lidar_info(NULL) accepted");
 }
 
 /* argument validation that needs no device (the CPU-container case) */
@@ -229,6 +376,7 @@ static void no_device_paths(void) {
     so[1].t_world_obj[0] = inf;
     CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(inf pose) accepted");
   }
+  lidar_no_device_paths();
   dsr_ctx* c = NULL;
   const int rc2 = dsr_ctx_create(-7, &c);
   CHECK(rc2 < 0 && c == NULL, "ctx_create(-7) = %d", rc2);
@@ -526,6 +674,59 @@ int main(int argc, char** argv) {
     CHECK(dsr_batch_refill(bt, n_obj, in) < 0, "refill of an ordinary batch accepted");
     CHECK(dsr_batch_destroy(bt) == 0, "destroy");
     free(rev);
+  }
+
+  /* LiDAR ingest: the device kernels against the hand-computed scene, and a capacity batch
+     refilled from the sweep against the same batch refilled from the host rule's arrays */
+  if (run_section("lidar")) {
+    lidar_scene s;
+    lidar_scene_make(&s);
+    float hp[2][9], hr[2][3 * 203], hz[2][3], dp[2][9], dr[2][3 * 203], dz[2][3];
+    dsr_lidar_det_out ho[2], dv[2];
+    dsr_lidar_det dets[3] = {s.det, s.det, s.det};  /* (the third only for the call with n_det 3 below) */
+    dets[1].trans[0] = -8.f;                        /* behind the camera: an empty object */
+    memset(hp, 0, sizeof hp), memset(hr, 0, sizeof hr), memset(hz, 0, sizeof hz);
+    memset(dp, 0, sizeof dp), memset(dr, 0, sizeof dr), memset(dz, 0, sizeof dz);
+    CHECK(dsr_lidar_inputs_host(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 2, dets, &hp[0][0],
+                                &hr[0][0], &hz[0][0], ho) == 0, "lidar_inputs_host failed");
+    CHECK(dsr_lidar_inputs(ctx, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 2, dets, &dp[0][0],
+                           &dr[0][0], &dz[0][0], dv) == 0, "%s", dsr_last_error(ctx));
+    lidar_scene_check(dp[0], dr[0], dz[0], &dv[0]);
+    CHECK(dv[1].status == DSR_LIDAR_BEHIND && dv[1].n_crop == 0 && dv[1].n_bg == 0, "lidar: behind %d", dv[1].status);
+    CHECK(memcmp(ho, dv, sizeof ho) == 0 && memcmp(hp[0], dp[0], sizeof hp[0]) == 0 && memcmp(hr, dr, sizeof hr) == 0 &&
+              memcmp(hz[0], dz[0], sizeof hz[0]) == 0, "lidar: device differs from host");
+    CHECK(dsr_lidar_inputs(ctx, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 2, s.inst, 2, s.masks, 2, dets, &dp[0][0],
+                           &dr[0][0], &dz[0][0], dv) < 0 && strlen(dsr_last_error(ctx)) > 0, "lidar: stride 2 accepted");
+    dsr_batch* bt = NULL;
+    dsr_object_out lo[2], fo[2];
+    CHECK(dsr_batch_create_capacity(ctx, dec, &p, 2, 8, 256, 0, &bt) == 0, "%s", dsr_last_error(ctx));
+    CHECK(dsr_batch_lidar_info(bt, dv) < 0, "lidar_info before a sweep refill accepted");
+    s.par.max_pts = 9;
+    CHECK(dsr_batch_refill_lidar(bt, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 2, dets) < 0,
+          "refill_lidar beyond max_pts accepted");
+    s.par.max_pts = 3;
+    CHECK(dsr_batch_refill_lidar(bt, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 3, dets) < 0,
+          "refill_lidar beyond the object capacity accepted");
+    CHECK(dsr_batch_refill_lidar(bt, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 2, dets) == 0, "%s",
+          dsr_last_error(ctx));
+    CHECK(dsr_batch_run(bt) == 0 && dsr_batch_download(bt, lo) == 0, "%s", dsr_last_error(ctx));
+    memset(dv, 0, sizeof dv);
+    CHECK(dsr_batch_lidar_info(bt, dv) == 0 && memcmp(ho, dv, sizeof ho) == 0, "lidar: batch records differ");
+    dsr_object_in fin[2];
+    memset(fin, 0, sizeof fin);
+    for (int d = 0; d < 2; ++d) {
+      const int ok = ho[d].status == DSR_LIDAR_OK;
+      memcpy(fin[d].t_cam_obj, ho[d].t_cam_obj, sizeof fin[d].t_cam_obj);
+      fin[d].pts = hp[d], fin[d].n_pts = ok ? ho[d].n_pts : 0;
+      fin[d].rays = hr[d], fin[d].n_rays = ok ? ho[d].n_pts + ho[d].n_bg : 0;
+      fin[d].depth = hz[d], fin[d].n_depth = ok ? ho[d].n_pts : 0;
+    }
+    CHECK(dsr_batch_refill(bt, 2, fin) == 0, "%s", dsr_last_error(ctx));
+    CHECK(dsr_batch_lidar_info(bt, dv) < 0, "lidar_info after a plain refill accepted");
+    CHECK(dsr_batch_run(bt) == 0 && dsr_batch_download(bt, fo) == 0, "%s", dsr_last_error(ctx));
+    CHECK(same_out(lo, fo, 2), "lidar: sweep refill differs from the host arrays' refill");
+    CHECK(!lo[1].is_good, "lidar: an empty object converged");
+    CHECK(dsr_batch_destroy(bt) == 0, "destroy");
   }
 
   /* graph capture and replays */

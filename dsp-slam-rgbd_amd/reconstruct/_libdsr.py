@@ -214,6 +214,37 @@ FRAME_POSE_STATUS = {0: "ok", 1: "not asked (the detection brought its pose)", 2
                      3: "fewer than min_points points", 4: "degenerate cuboid (l == 0 or a non-finite value)"}
 
 
+class LidarParams(C.Structure):
+    """dsr_lidar_params: every value is taken literally (dsr_lidar_params_default fills the defaults)."""
+    _fields_ = [("max_pts", C.c_int), ("max_bg", C.c_int), ("downsample", C.c_int), ("expand", C.c_int),
+                ("min_mask_area", C.c_int), ("radius", C.c_float), ("box_margin", C.c_float)]
+
+
+class LidarMask(C.Structure):
+    """dsr_lidar_mask: a label of the instance image and an optional box (bbox[2] < bbox[0]: the
+    mask's tight box)."""
+    _fields_ = [("label", C.c_int), ("bbox", C.c_int * 4)]
+
+
+class LidarDet(C.Structure):
+    """dsr_lidar_det: a 3-D detector row (trans, size = (w, l, h), theta) and the code of dsr_object_in."""
+    _fields_ = [("trans", C.c_float * 3), ("size", C.c_float * 3), ("theta", C.c_float), ("code", FP)]
+
+
+class LidarDetOut(C.Structure):
+    """dsr_lidar_det_out: the ingest record of one detection."""
+    _fields_ = [("status", C.c_int), ("n_near", C.c_int), ("n_crop", C.c_int), ("n_pts", C.c_int),
+                ("n_proj", C.c_int), ("mask", C.c_int), ("n_hits", C.c_int), ("n_mask_px", C.c_int),
+                ("n_bg", C.c_int), ("box", C.c_int * 4), ("grid_h", C.c_int), ("grid_w", C.c_int),
+                ("t_cam_obj", C.c_float * 16)]
+
+
+LIDAR_MAX_MASKS = 256    # include/dsr.h DSR_LIDAR_MAX_MASKS
+LIDAR_OK, LIDAR_BEHIND, LIDAR_NO_POINTS, LIDAR_NO_MATCH, LIDAR_SMALL_MASK = 0, 1, 2, 3, 4   # include/dsr.h DSR_LIDAR_*
+LIDAR_STATUS = {0: "ok", 1: "behind the camera", 2: "no sweep point in the box",
+                3: "no mask holds more than half of the projected points", 4: "mask of at most min_mask_area pixels"}
+
+
 #: dsr_batch_lite_diag record layout (csrc/dsr_dev.hpp: STD_*)
 LITE_DIAG_FIELDS = ("broken_blocks", "recorded", "block", "wave", "counter", "target", "observed", "tile_iter",
                     "hw_id", "xcc_id", "polls", "real_ticks")
@@ -303,6 +334,16 @@ SIGNATURES = {
     "dsr_batch_refill_frame_poses": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams),
                                                C.POINTER(FramePoseParams), FP, IP, C.c_int, C.POINTER(FrameDet), IP]),
     "dsr_batch_frame_pose_info": (C.c_int, [C.c_void_p, C.POINTER(FramePoseOut)]),
+    "dsr_lidar_params_default": (C.c_int, [C.POINTER(LidarParams)]),
+    "dsr_lidar_inputs_host": (C.c_int, [C.POINTER(Camera), C.POINTER(LidarParams), FP, FP, C.c_int, C.c_int, IP,
+                                        C.c_int, C.POINTER(LidarMask), C.c_int, C.POINTER(LidarDet), FP, FP, FP,
+                                        C.POINTER(LidarDetOut)]),
+    "dsr_lidar_inputs": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(LidarParams), FP, FP, C.c_int, C.c_int,
+                                   IP, C.c_int, C.POINTER(LidarMask), C.c_int, C.POINTER(LidarDet), FP, FP, FP,
+                                   C.POINTER(LidarDetOut)]),
+    "dsr_batch_refill_lidar": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(LidarParams), FP, FP, C.c_int,
+                                         C.c_int, IP, C.c_int, C.POINTER(LidarMask), C.c_int, C.POINTER(LidarDet)]),
+    "dsr_batch_lidar_info": (C.c_int, [C.c_void_p, C.POINTER(LidarDetOut)]),
 }
 
 #: entry points added without an ABI number change: callers detect them by the symbol, so a
@@ -312,7 +353,8 @@ BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_rende
              "dsr_frame_inputs", "dsr_batch_refill_frame", "dsr_batch_frame_info", "dsr_scene_create",
              "dsr_scene_set_objects", "dsr_scene_query", "dsr_scene_peek", "dsr_scene_stats_get", "dsr_scene_destroy",
              "dsr_scene_bin_host", "dsr_frame_pose_params_default", "dsr_frame_poses_host", "dsr_frame_poses",
-             "dsr_batch_refill_frame_poses", "dsr_batch_frame_pose_info")
+             "dsr_batch_refill_frame_poses", "dsr_batch_frame_pose_info", "dsr_lidar_params_default",
+             "dsr_lidar_inputs_host", "dsr_lidar_inputs", "dsr_batch_refill_lidar", "dsr_batch_lidar_info")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

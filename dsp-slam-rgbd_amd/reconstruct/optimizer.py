@@ -18,6 +18,10 @@ runs in libdsr's HIP kernels on an MI355X (``include/dsr.h``):
 * ``Optimizer.reconstruct_frame(depth, instance, detections, camera)`` — NEW: a keyframe straight
   from a depth image and an instance-label image; device kernels build every detection's points
   and rays in the slots of a capacity batch -> ``dsr_batch_refill_frame``.
+* ``Optimizer.reconstruct_lidar_frame(velo, instance, masks, detections, camera, t_cam_velo)`` —
+  NEW: a KITTI keyframe straight from its Velodyne sweep, the 3-D detector's boxes and the
+  instance-label image (kitti_sequence.py:99-216 on the device) -> ``dsr_batch_refill_lidar``
+  (DESIGN.md §3.5d).
 * ``Optimizer.compute_sdf_loss_objectpoint_zhjd(pts_obj, code)`` —
   optimizer.py:207-213 -> ``dsr_sdf_eval``.
 * ``Optimizer.estimate_pose_cam_obj(...)`` — optimizer.py:46-87 -> ``dsr_pose_only``.
@@ -388,6 +392,62 @@ class Optimizer(object):
             r["fail_reason"] = L.FAIL_REASONS.get(int(outs[k].fail_reason), "?")
             r["ingest"] = U.frame_record(recs[k])
             r["pose_init"] = U.frame_pose_record(precs[k]) if poses else given_record(hyp[k], r["ingest"])
+            res.append(r)
+        return self._mesh_results(res, mesher)
+
+    def reconstruct_lidar_frame(self, velo, instance, masks, detections, camera, t_cam_velo, mesher=None, **params):
+        """One KITTI keyframe straight from its Velodyne sweep, the 3-D detector's boxes and the
+        instance-label image with its mask list: what ``reconstruct_keyframe`` returns for the
+        inputs ``reconstruct.utils.lidar_inputs`` builds, without building them on the host.  The
+        sweep and the image are uploaded once and device kernels crop, sub-sample, project,
+        associate and fill the slots of a fixed-capacity batch (dsr_batch_refill_lidar; the rule is
+        DESIGN.md §3.5d, replacing FrameWithLiDAR.get_detections, kitti_sequence.py:99-216, before
+        CreateNewMapObjects_foronlyStereo, LocalMapping_util.cc:156-208).  ``masks``:
+        ``utils.lidar_masks``; ``detections``: ``utils.lidar_dets``; ``camera``:
+        ``utils.frame_camera``; ``params``: ``utils.LIDAR_PARAM_NAMES`` (the slot's capacity comes
+        from max_pts / max_bg).  Every result carries the detection's ingest record as ``ingest``
+        (``utils.lidar_record``); a detection that is not ok fails like an empty object.  There are
+        no flipped hypotheses: the 3-D detector supplies the heading.  With ``keyframe_mode``
+        "oneshot", or when no slot is within the capacity bounds, the inputs are built on the host
+        (``lidar_inputs``) and run through ``reconstruct_keyframe``: bitwise the same results."""
+        from reconstruct import utils as U
+
+        cam = U.frame_camera(camera)
+        p = U.lidar_params(**params)
+        velo, instance, tcv = U.lidar_sweep(velo, instance, cam, t_cam_velo)
+        n = len(detections)
+        if n == 0:
+            return []
+        ctx = self._ctx
+        slot = None
+        if hasattr(ctx.lib, "dsr_batch_refill_lidar") and p.max_pts >= 1 and p.max_bg >= 0:
+            slot = self._slot_for_caps(n, p.max_pts, p.max_pts + p.max_bg, n * (p.max_pts + p.max_bg))
+        if slot is None:
+            objects, records = U.lidar_inputs(velo, instance, masks, detections, cam, tcv, **params)
+            res = self.reconstruct_keyframe([ob + (True,) for ob in objects], mesher)
+            for r, rec in zip(res, records):
+                r["ingest"] = rec
+            return res
+        dets, keep = U.lidar_dets(detections, self.code_len)
+        ml = U.lidar_masks(masks)
+        outs = (L.ObjectOut * n)()
+        recs = (L.LidarDetOut * n)()
+        ctx.check(ctx.lib.dsr_batch_refill_lidar(slot.handle, cam, p, L.fptr(tcv), L.fptr(velo), velo.shape[0],
+                                                 velo.shape[1], L.iptr(instance), len(masks), ml, n, dets),
+                  "dsr_batch_refill_lidar")
+        slot.busy = True
+        try:
+            ctx.check(ctx.lib.dsr_batch_run(slot.handle), "dsr_batch_run")
+            ctx.check(ctx.lib.dsr_batch_download(slot.handle, outs), "dsr_batch_download")
+            ctx.check(ctx.lib.dsr_batch_lidar_info(slot.handle, recs), "dsr_batch_lidar_info")
+        finally:
+            slot.busy = False
+        res = []
+        for k in range(n):
+            r = self._result(outs[k], self.code_len)
+            r["iters_done"] = int(outs[k].iters_done)
+            r["fail_reason"] = L.FAIL_REASONS.get(int(outs[k].fail_reason), "?")
+            r["ingest"] = U.lidar_record(recs[k])
             res.append(r)
         return self._mesh_results(res, mesher)
 

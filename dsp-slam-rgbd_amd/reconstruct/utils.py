@@ -329,6 +329,137 @@ def frame_poses(depth, instance, detections, camera, pose_params=None, **params)
     return objects, records, poses
 
 
+LIDAR_PARAM_NAMES = ("max_pts", "max_bg", "downsample", "expand", "min_mask_area", "radius", "box_margin")
+
+
+def lidar_params(**params):
+    """``dsr_lidar_params``: the library's defaults (dsr_lidar_params_default: max_pts 250, max_bg
+    200, downsample 4, expand 5, min_mask_area 1000, radius 3.0, box_margin 1.1) with ``params`` on
+    top."""
+    from reconstruct import _libdsr as L
+
+    unknown = set(params) - set(LIDAR_PARAM_NAMES)
+    if unknown:
+        raise TypeError(f"unknown lidar parameters: {sorted(unknown)}")
+    p = L.LidarParams()
+    if L.load_library().dsr_lidar_params_default(p) != 0:
+        raise L.DsrError("dsr_lidar_params_default failed")
+    for k, v in params.items():
+        setattr(p, k, float(v) if k in ("radius", "box_margin") else int(v))
+    return p
+
+
+def lidar_dets(detections, code_len=64):
+    """The ``dsr_lidar_det`` array of a list of detections — dicts ``{trans, size = (w, l, h), theta,
+    code=None}`` or rows ``(x, y, z, w, l, h, theta, ...)`` as the 3-D detector emits them
+    (kitti_sequence.py:116) — and the arrays it points into."""
+    from reconstruct import _libdsr as L
+
+    n = len(detections)
+    dets = (L.LidarDet * max(n, 1))()
+    keep = []
+    for i, det in enumerate(detections):
+        if isinstance(det, dict):
+            row = [*det["trans"], *det["size"], det["theta"]]
+            code = det.get("code")
+        else:
+            row, code = list(det)[:7], None
+        row = np.asarray(row, np.float32).reshape(7)
+        dets[i].trans[:] = row[:3].tolist()
+        dets[i].size[:] = row[3:6].tolist()
+        dets[i].theta = float(row[6])
+        if code is not None:
+            c = np.ascontiguousarray(np.asarray(code, np.float32).reshape(-1)[:code_len])
+            if c.shape[0] != code_len:
+                raise ValueError(f"code must hold at least {code_len} values, got {c.shape[0]}")
+            keep.append(c)
+            dets[i].code = L.fptr(c)
+    return dets, keep
+
+
+def lidar_masks(masks):
+    """The ``dsr_lidar_mask`` array of a list of masks: dicts ``{label, bbox=None}``, pairs
+    ``(label, bbox)`` or bare labels (``bbox`` None: the mask's tight box)."""
+    from reconstruct import _libdsr as L
+
+    n = len(masks)
+    out = (L.LidarMask * max(n, 1))()
+    for i, m in enumerate(masks):
+        if isinstance(m, dict):
+            label, bbox = m["label"], m.get("bbox")
+        elif isinstance(m, (tuple, list)):
+            label, bbox = m
+        else:
+            label, bbox = m, None
+        out[i].label = int(label)
+        out[i].bbox[:] = [0, 0, -1, -1] if bbox is None else [int(x) for x in bbox]
+    return out
+
+
+def lidar_record(o):
+    """A ``dsr_lidar_det_out`` as a dict; ``t_cam_obj`` as a tuple of its 16 row-major values, so
+    that records compare with ``==``."""
+    return ForceKeyErrorDict(status=int(o.status), n_near=int(o.n_near), n_crop=int(o.n_crop), n_pts=int(o.n_pts),
+                             n_proj=int(o.n_proj), mask=int(o.mask), n_hits=int(o.n_hits),
+                             n_mask_px=int(o.n_mask_px), n_bg=int(o.n_bg), box=tuple(o.box), grid_h=int(o.grid_h),
+                             grid_w=int(o.grid_w), t_cam_obj=tuple(o.t_cam_obj))
+
+
+def lidar_sweep(velo, instance, camera, t_cam_velo):
+    """The sweep as a contiguous (n, stride >= 3) float32 array, the instance image as frame_images
+    wants it and t_cam_velo as 16 float32."""
+    velo = np.ascontiguousarray(np.asarray(velo), dtype=np.float32)
+    if velo.ndim != 2 or velo.shape[1] < 3:
+        raise ValueError(f"velo {velo.shape} must be (n, stride >= 3)")
+    instance = np.ascontiguousarray(np.asarray(instance), dtype=np.int32)
+    if instance.shape != (camera.height, camera.width):
+        raise ValueError(f"instance {instance.shape} must be (height, width) = {(camera.height, camera.width)}")
+    tcv = np.ascontiguousarray(np.asarray(t_cam_velo, np.float32).reshape(16))
+    return velo, instance, tcv
+
+
+def lidar_inputs(velo, instance, masks, detections, camera, t_cam_velo, **params):
+    """What ``FrameWithLiDAR.get_detections`` builds per 3-D detection on the CPU
+    (kitti_sequence.py:99-216, with ``pixels_sampler`` :70-92 and ``get_rays``,
+    loss_utils.py:23-37) — from a Velodyne sweep ``velo`` (n, stride >= 3), an instance-label image
+    and its mask list, by the exact rule of DESIGN.md §3.5d (``dsr_lidar_inputs_host``: plain C++
+    on the host, no device).  ``masks``: see ``lidar_masks``; ``detections``: see ``lidar_dets``;
+    ``camera``: see ``frame_camera``; ``t_cam_velo``: rigid 4x4; ``params``: ``LIDAR_PARAM_NAMES``.
+    Returns ``(objects, records)`` shaped like ``frame_inputs``: per detection ``(t_cam_obj, pts,
+    rays, depth, code)`` — the tuple ``Optimizer.reconstruct_objects`` takes — and its ingest record
+    (``lidar_record``).  A detection that is not ok has empty arrays (the reference's ``rays =
+    None``)."""
+    from reconstruct import _libdsr as L
+
+    lib = L.load_library()
+    cam = frame_camera(camera)
+    p = lidar_params(**params)
+    velo, instance, tcv = lidar_sweep(velo, instance, cam, t_cam_velo)
+    n = len(detections)
+    dets, keep = lidar_dets(detections)
+    ml = lidar_masks(masks)
+    mp, mr = max(p.max_pts, 0), max(p.max_pts, 0) + max(p.max_bg, 0)
+    pts = np.zeros((max(n, 1), mp, 3), np.float32)
+    rays = np.zeros((max(n, 1), mr, 3), np.float32)
+    dobs = np.zeros((max(n, 1), mp), np.float32)
+    out = (L.LidarDetOut * max(n, 1))()
+    rc = lib.dsr_lidar_inputs_host(cam, p, L.fptr(tcv), L.fptr(velo), velo.shape[0], velo.shape[1], L.iptr(instance),
+                                   len(masks), ml, n, dets, L.fptr(pts), L.fptr(rays), L.fptr(dobs), out)
+    if rc != 0:
+        raise L.DsrError(f"dsr_lidar_inputs_host failed ({rc}): bad camera, sweep, masks, detections or lidar "
+                         "parameters")
+    objects, records = [], []
+    for i, det in enumerate(detections):
+        r = lidar_record(out[i])
+        ok = r.status == L.LIDAR_OK
+        n_p, n_r = (r.n_pts, r.n_pts + r.n_bg) if ok else (0, 0)
+        code = det.get("code") if isinstance(det, dict) else None
+        objects.append((np.asarray(r.t_cam_obj, np.float32).reshape(4, 4), pts[i, :n_p].copy(), rays[i, :n_r].copy(), dobs[i, :n_p].copy(),
+                        None if code is None else np.asarray(code, np.float32)))
+        records.append(r)
+    return objects, records
+
+
 def create_voxel_grid(vol_dim=128):
     """utils.py:97-116.  Note the reference's ``LongTensor / vol_dim`` is TRUE division
     in torch >= 1.6 (fp32), so its x/y columns are not integer lattice indices; this

@@ -725,6 +725,123 @@ int dsr_batch_refill_frame_poses(dsr_batch* b, const dsr_camera* cam, const dsr_
  * was not of this kind.  dsr_batch_frame_info still returns the ingest records. */
 int dsr_batch_frame_pose_info(dsr_batch* b, dsr_frame_pose_out* out);
 
+/* ---- LiDAR keyframe ingest: one Velodyne sweep + the 3-D detector's boxes + one instance-label
+ * image and its mask list -> every detection's surface points, rays, observed depths and start
+ * pose, on the host or straight into the slots of a capacity batch on the device.  Replaces the
+ * per-detection numpy of FrameWithLiDAR.get_detections (reconstruct/kitti_sequence.py:99-216: the
+ * 3 m cube and widened-box crop :118-138, the sub-sampling :139-143, the camera points and pose
+ * :144-146, the projection and mask association :183-198, the background rays :200-210 with
+ * pixels_sampler :70-92 and get_rays, reconstruct/loss_utils.py:23-37), whose result the C++ side
+ * takes in Tracking::GetObjectDetectionsLiDAR (src/Tracking_util.cc:31-58).  DESIGN.md 3.5d states
+ * the rule exactly; callers detect these entry points by symbol, the ABI number is unchanged.
+ *
+ * Per detection (fp64 on the fp32 inputs, every stored value rounded to fp32 once): c = cos theta,
+ * s = sin theta, R = [[c,0,-s],[-s,0,-c],[0,1,0]], o = (x, y, z + h/2), A = R^T, t = -R^T o,
+ * lo = trans - radius, hi = trans + radius, e = (m w/2, h/2, m l/2) with m = box_margin, and
+ * t_cam_obj = t_cam_velo [m l/2 R | o] (kitti_sequence.py:145-146 scales by the widened l).  A
+ * sweep point p is near when lo_k < p_k < hi_k for all k and in when also -e_k < x_k < e_k with
+ * x_k = fmaf(A_k0, p_x, fmaf(A_k1, p_y, fmaf(A_k2, p_z, t_k))) in fp32 (strict inequalities; a NaN
+ * coordinate is in nothing).  The in-points in sweep order are the n_crop candidates; n_pts =
+ * min(n_crop, max_pts) rows are kept, row i from candidate sel(i, n_pts, n_crop) (the integer sel of
+ * the frame ingest above).  A row's surface point is q = t_cam_velo p (the same nested fmaf), its
+ * observed depth q_z, its foreground ray (q_x / q_z, q_y / q_z, 1).  Rows with q_z > 0 whose pixel
+ * (fmaf(fx, r_x, cx), fmaf(fy, r_y, cy)) lies strictly inside (0, W) x (0, H) are the n_proj
+ * projected rows; each counts one hit for the first mask-list entry whose label the instance image
+ * carries at the truncated pixel.  The first entry with the most hits is matched when 2 hits >
+ * n_proj.  Background rays come from the matched mask exactly as the frame ingest draws them from a
+ * detection's label and box, and follow the foreground rays with observed depth 0.  Points, rays,
+ * depths and t_cam_obj are written for every detection (the reference returns surface_points and
+ * T_cam_obj for unmatched instances too; estimate_pose_cam_obj consumes them,
+ * LocalMapping_util.cc:103-110); background rays only when the status is DSR_LIDAR_OK, and in a
+ * batch slot a detection that is not OK is an empty object (the reference's rays = None,
+ * LocalMapping_util.cc:173).  Out of scope: the occlusion masks of kitti_sequence.py:177-216
+ * (computed, never read) and the depth-order sort :112-113 that only feeds them, overlapping masks
+ * (a label image holds one label per pixel), the detectors themselves, and get_colored_pts. */
+#define DSR_LIDAR_MAX_MASKS 256
+typedef struct {
+  int max_pts;                    /* surface points = foreground rays kept per detection (250, num_lidar_max) */
+  int max_bg;                     /* background rays kept per detection (200) */
+  int downsample;                 /* background grid stride (4) */
+  int expand;                     /* box growth in pixels (5) */
+  int min_mask_area;              /* masks of at most this many pixels are skipped (1000) */
+  float radius;                   /* half edge of the cube around trans (3.0, kitti_sequence.py:125) */
+  float box_margin;               /* widening of w and l (1.1, kitti_sequence.py:133-134) */
+} dsr_lidar_params;
+typedef struct {
+  int label;                      /* the mask's value in the instance image */
+  int bbox[4];                    /* l, t, r, b inclusive; bbox[2] < bbox[0]: the mask's tight box */
+} dsr_lidar_mask;
+typedef struct {
+  float trans[3];                 /* box centre x, y and bottom z, velodyne frame (a PointPillars row) */
+  float size[3];                  /* w, l, h */
+  float theta;                    /* heading */
+  const float* code;              /* as dsr_object_in: (code_len,) or NULL */
+} dsr_lidar_det;
+enum {
+  DSR_LIDAR_OK = 0,
+  DSR_LIDAR_BEHIND = 1,           /* t_cam_obj[2][3] <= 0 (is_front, kitti_sequence.py:154, :181) */
+  DSR_LIDAR_NO_POINTS = 2,        /* n_crop == 0 */
+  DSR_LIDAR_NO_MATCH = 3,         /* no mask holds more than half of the projected rows (:195) */
+  DSR_LIDAR_SMALL_MASK = 4        /* n_mask_px <= min_mask_area (:200) */
+};
+typedef struct {
+  int status;                     /* DSR_LIDAR_*: the first condition that applies, in the enum's order */
+  int n_near, n_crop;             /* sweep points in the cube / also in the widened box */
+  int n_pts;                      /* rows written: points, depths and foreground rays (every status) */
+  int n_proj;                     /* rows projected into the image */
+  int mask;                       /* index of the matched mask-list entry, or -1 */
+  int n_hits;                     /* hits of the first entry with the most (0 without masks) */
+  int n_mask_px;                  /* pixels carrying the matched label (0 unmatched) */
+  int n_bg;                       /* background rays written (0 unless OK) */
+  int box[4];                     /* the matched mask's expanded box; 0, 0, -1, -1 when there is none */
+  int grid_h, grid_w;
+  float t_cam_obj[16];
+} dsr_lidar_det_out;
+
+/* Host only: max_pts 250, max_bg 200, downsample 4, expand 5, min_mask_area 1000, radius 3.0,
+ * box_margin 1.1 (kitti_sequence.py:70-92, :125, :133-134, :141, :203).  Every other call takes the
+ * values literally. */
+int dsr_lidar_params_default(dsr_lidar_params* p);
+/* The rule in plain C++ on the host — no context, no device (replaces get_detections,
+ * kitti_sequence.py:99-216).  velo: n_velo rows of stride >= 3 floats, x y z first (KITTI's .bin is
+ * stride 4); t_cam_velo: 4 x 4 row-major, rigid; instance: height x width; masks: n_masks entries
+ * (a label listed twice is only ever matched by its first entry).  Fixed strides per detection as
+ * dsr_frame_inputs_host: pts max_pts x 3, rays (max_pts + max_bg) x 3, dobs max_pts; rows beyond a
+ * detection's counts are left untouched; out: n_det records in the caller's order.  Returns < 0
+ * (no message: there is no context) for the argument errors of dsr_frame_inputs_host that apply, a
+ * t_cam_velo that is not rigid, stride < 3, n_velo < 0 or > 2^24, n_masks outside 0 ..
+ * DSR_LIDAR_MAX_MASKS, a non-finite detection field, a size component <= 0, and a radius or
+ * box_margin that is not positive and finite. */
+int dsr_lidar_inputs_host(const dsr_camera* cam, const dsr_lidar_params* params, const float* t_cam_velo,
+                          const float* velo, int n_velo, int stride, const int* instance, int n_masks,
+                          const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
+                          float* rays, float* dobs, dsr_lidar_det_out* out);
+/* The same arrays and records produced by the device kernels (k_lidar_*, csrc/dsr_lidar.hpp) and
+ * copied back: bitwise those of dsr_lidar_inputs_host (get_detections as above). */
+int dsr_lidar_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_lidar_params* params,
+                     const float* t_cam_velo, const float* velo, int n_velo, int stride, const int* instance,
+                     int n_masks, const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
+                     float* rays, float* dobs, dsr_lidar_det_out* out);
+/* dsr_batch_refill from a sweep (the KITTI call site: get_detections, kitti_sequence.py:99-216,
+ * then CreateNewMapObjects_foronlyStereo, src/LocalMapping_util.cc:156-208, without the host
+ * arrays): the sweep, the image, the mask list and the prepared detections go through pinned
+ * staging onto the context stream, ordered after the previous run; the kernels write slot i's pts /
+ * rays / dobs rows and its counts in device memory for detection i, whose pose row is the rule's
+ * t_cam_obj; slots >= n_det and detections that are not DSR_LIDAR_OK are empty objects.  No
+ * argument of the run changes, so a DSR_BATCH_GRAPH batch keeps replaying its one graph.  Errors,
+ * returned before the device is touched: those of dsr_lidar_inputs_host, a batch that is not a
+ * capacity batch, n_det above its slot count, max_pts above its max_pts, max_pts + max_bg above
+ * its max_rays.  The buffers grow with the sweep and the image, belong to the batch and are freed
+ * with it. */
+int dsr_batch_refill_lidar(dsr_batch* b, const dsr_camera* cam, const dsr_lidar_params* params,
+                           const float* t_cam_velo, const float* velo, int n_velo, int stride,
+                           const int* instance, int n_masks, const dsr_lidar_mask* masks, int n_det,
+                           const dsr_lidar_det* dets);
+/* Waits for the last dsr_batch_refill_lidar and copies its n_det records (what get_detections
+ * reports through num_surface_points, mask and rays = None, kitti_sequence.py:148-157, :195-210);
+ * an error when the batch's last fill was not a sweep. */
+int dsr_batch_lidar_info(dsr_batch* b, dsr_lidar_det_out* out);
+
 /* ---- multi-GPU from one process: replaces the per-detection loop
  * LocalMapping_util.cc:165-206 spread over devices.  ctx[g] / dec[g] are one context and
  * its decoder per device; objects are LPT-partitioned (cost n_rays*M + n_pts), each
