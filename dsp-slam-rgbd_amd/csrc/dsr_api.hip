@@ -349,25 +349,26 @@ struct dsr_batch {
   };
   std::vector<Stage> stage;
   hipEvent_t up_ev = nullptr;       // recorded after the last refill's uploads
-  // Frame refills (dsr_batch_refill_frame): one pinned block (depth | instance | detections) and
-  // one device block (the same, then the kernels' row tables and records; dsr_frame.hpp), grown to
-  // the largest frame seen and freed with the batch.  frame_n: detections of the last fill if it
-  // was a frame, else -1.
-  void* frame_host = nullptr;
-  void* frame_dev = nullptr;
-  size_t frame_host_bytes = 0, frame_dev_bytes = 0;
-  int frame_n = -1, frame_w = 0, frame_h = 0;
-  // the last fill was dsr_batch_refill_frame_poses with this max_pts (§3.5c; its keep flags and pose
-  // records follow the ingest's part of frame_dev), else -1
-  int frame_pose_pts = -1;
-  // Sweep refills (dsr_batch_refill_lidar): one pinned block (sweep | instance | masks | prepared
-  // detections) and one device block (the same, then the kernels' tables and records;
-  // dsr_lidar.hpp), grown to the largest sweep and image seen and freed with the batch.
-  // lidar_shape.n_det: detections of the last fill if it was a sweep, else -1.
-  void* lidar_host = nullptr;
-  void* lidar_dev = nullptr;
-  size_t lidar_host_bytes = 0, lidar_dev_bytes = 0;
-  LidarShape lidar_shape{0, 3, 0, 0, -1};
+  // Device-filled refills (dsr_batch_refill_frame, _frame_poses, _lidar) share one ingest block: a
+  // pinned half (what the fill uploads — depth | instance | detections, or sweep | instance | masks |
+  // prepared detections) and a device half (the same, then the kernels' tables and records;
+  // dsr_frame.hpp, dsr_lidar.hpp).  A fill is of one kind, so the block is laid out for the last
+  // fill only; it grows to the largest fill seen (refill_begin) and is freed with the batch.
+  struct IngestBlock {
+    void* host = nullptr;
+    void* dev = nullptr;
+    size_t host_bytes = 0, dev_bytes = 0;
+  };
+  IngestBlock ingest;
+  // The last fill: its kind and what lays its part of the ingest block out.  Written by refill_end
+  // alone; the *_info entry points read it.
+  struct Fill {
+    enum Kind { OBJECTS, FRAME, FRAME_POSES, SWEEP };
+    Kind kind = OBJECTS;
+    LidarShape shape{0, 3, 0, 0, 0};   // n_det: every kind's objects; W, H: the image kinds; n_velo, stride: a sweep
+    int max_pts = 0;                   // FRAME_POSES: sizes the keep flags (§3.5c)
+  };
+  Fill last;
 };
 
 #define DSR_CHECK(ctx, call)                                                        \
@@ -1239,10 +1240,8 @@ int dsr_batch_destroy(dsr_batch* b) {
   if (b->graph) hipGraphExecDestroy(b->graph);
   for (auto& sg : b->stage)
     if (sg.host) hipHostFree(sg.host);
-  if (b->frame_host) hipHostFree(b->frame_host);
-  if (b->frame_dev) hipFree(b->frame_dev);
-  if (b->lidar_host) hipHostFree(b->lidar_host);
-  if (b->lidar_dev) hipFree(b->lidar_dev);
+  if (b->ingest.host) hipHostFree(b->ingest.host);
+  if (b->ingest.dev) hipFree(b->ingest.dev);
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (b->up_ev) ctx->ev_plain.push_back(b->up_ev);
   for (auto& e : b->ev)
@@ -1685,10 +1684,209 @@ int dsr_batch_create_capacity(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_op
   return 0;
 }
 
+// inverse of a rigid 4x4 (x_view = t_view_ref x_ref) in fp64, rounded once: [R^T | -R^T t].
+// False unless the last row is 0 0 0 1 and R^T R = I within 1e-4 with det R > 0.
+static bool rigid_inverse(const float* t, float* out) {
+  if (t[12] != 0.f || t[13] != 0.f || t[14] != 0.f || t[15] != 1.f) return false;
+  double R[3][3], tr[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[i][j] = (double)t[i * 4 + j];
+    tr[i] = (double)t[i * 4 + 3];
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < 3; ++k) s += R[k][i] * R[k][j];
+      if (!(std::fabs(s - (i == j ? 1.0 : 0.0)) <= 1e-4)) return false;       // (NaN fails too)
+    }
+  const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                     R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+  if (!(det > 0.0)) return false;
+  for (int i = 0; i < 3; ++i) {
+    if (!std::isfinite(tr[i])) return false;
+    for (int j = 0; j < 3; ++j) out[i * 4 + j] = (float)R[j][i];
+    out[i * 4 + 3] = (float)(-(R[0][i] * tr[0] + R[1][i] * tr[1] + R[2][i] * tr[2]));
+  }
+  out[12] = out[13] = out[14] = 0.f;
+  out[15] = 1.f;
+  return true;
+}
+
+// ------------------------------------------------------------------------------------
+// ingest: what fills a capacity batch (host arrays, a frame, a frame with start poses, a sweep) and
+// the one-call forms of the device ingests (include/dsr.h)
+// ------------------------------------------------------------------------------------
+// ---- the shared forms
+// A refill is: the entry point's refusals; refill_begin; the kind packs its ingest block and says
+// what every filled slot stages; refill_upload; the kind's kernels; refill_end.
+static int refill_needs_capacity(dsr_batch* b, const char* who) {
+  if (b->capacity) return 0;
+  return fail(b->ctx, std::string("dsr_batch_") + who + " needs a batch from dsr_batch_create_capacity");
+}
+
+// the refusals of a device-filled kind, after its own argument errors
+static int refill_fits(dsr_batch* b, const char* who, int n_det, int max_pts, int max_bg) {
+  const std::string w(who);
+  if (n_det > b->n_obj) return fail(b->ctx, w + ": n_det exceeds the batch's object capacity");
+  if (max_pts > b->max_pts) return fail(b->ctx, w + ": max_pts exceeds the batch's max_pts");
+  if ((long long)max_pts + max_bg > b->max_rays) return fail(b->ctx, w + ": max_pts + max_bg exceeds the batch's max_rays");
+  return 0;
+}
+
+namespace {   // (internal linkage, as BatchDeleter: the library exports no symbol for these)
+// what one filled slot stages: the counts (zero where the ingest kernels write them), the pose
+// (null: the identity, as in an empty slot), the code (null: zeros) and pose_is_obj_cam
+struct SlotFill {
+  int n_pts = 0, n_rays = 0, n_fg = 0;
+  const float* pose = nullptr;
+  const float* code = nullptr;
+  bool is_oc = false;
+};
+
+// The round trip of a one-call ingest (n_det > 0): the packed block and the caller's pts | rays |
+// dobs (| t_in) go up, the entry point launches its kernels if upload() says so, the arrays and
+// the records come back, and finish() synchronises the stream before the arena frees.  The first
+// HIP error is the call's: -1 with its text.
+struct IngestCall {
+  dsr_ctx* ctx;
+  hipStream_t s;
+  float *pts, *rays, *dobs;                        // the caller's arrays
+  size_t np, nr, nz;                               // their lengths
+  DevArena mem;
+  char* dev = nullptr;                             // the ingest block
+  float* o = nullptr;                              // pts | rays | dobs | t_in on the device
+  int rc = 0;
+  IngestCall(dsr_ctx* c, int n_det, int max_pts, int max_bg, float* p, float* r, float* d)
+      : ctx(c), s(c->stream), pts(p), rays(r), dobs(d), np((size_t)n_det * max_pts * 3),
+        nr((size_t)n_det * ((size_t)max_pts + max_bg) * 3), nz((size_t)n_det * max_pts) {}
+  float* d_pts() const { return o; }
+  float* d_rays() const { return o + np; }
+  float* d_dobs() const { return o + np + nr; }
+  float* d_tin() const { return o + np + nr + nz; }
+  bool chk(hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == 0) {
+      ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+      rc = -1;
+    }
+    return e == hipSuccess;
+  }
+  void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    chk(hipMemcpyAsync(dst, src, bytes, kind, s), "hipMemcpyAsync");
+  }
+  // true: the kernels may run
+  bool upload(const char* kind, const std::vector<char>& host, size_t all, const std::vector<float>& tin = {}) {
+    if (!mem.alloc(&dev, all) || !mem.alloc(&o, np + nr + nz + tin.size())) {
+      ctx->err = std::string("hipMalloc failed (") + kind + ")";
+      rc = -1;
+      return false;
+    }
+    // rows beyond a detection's counts come back as the caller had them
+    copy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    copy(d_pts(), pts, sizeof(float) * np, hipMemcpyHostToDevice);
+    copy(d_rays(), rays, sizeof(float) * nr, hipMemcpyHostToDevice);
+    copy(d_dobs(), dobs, sizeof(float) * nz, hipMemcpyHostToDevice);
+    if (!tin.empty()) copy(d_tin(), tin.data(), sizeof(float) * tin.size(), hipMemcpyHostToDevice);
+    return rc == 0;
+  }
+  void download(const char* kernels) {
+    chk(hipGetLastError(), kernels);
+    copy(pts, d_pts(), sizeof(float) * np, hipMemcpyDeviceToHost);
+    copy(rays, d_rays(), sizeof(float) * nr, hipMemcpyDeviceToHost);
+    copy(dobs, d_dobs(), sizeof(float) * nz, hipMemcpyDeviceToHost);
+  }
+  void records(void* out, const void* recs, size_t bytes) { copy(out, recs, bytes, hipMemcpyDeviceToHost); }
+  int finish() {
+    if (o) chk(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return rc;
+  }
+};
+}  // namespace
+
+// Waits until the previous refill's copies have left the staging buffers and the pinned block,
+// then makes the ingest block hold `up` uploaded bytes of `all` (0, 0: a fill without one).  Both
+// halves only grow; the device block is replaced only once no kernel can still read it.
+static int refill_begin(dsr_batch* b, size_t up, size_t all) {
+  dsr_ctx* ctx = b->ctx;
+  dsr_batch::IngestBlock& g = b->ingest;
+  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+  if (up > g.host_bytes) {
+    if (g.host) hipHostFree(g.host);
+    g.host = nullptr;
+    g.host_bytes = 0;
+    DSR_CHECK(ctx, hipHostMalloc(&g.host, up, hipHostMallocDefault));
+    g.host_bytes = up;
+  }
+  if (all > g.dev_bytes) {
+    // the kernels of an earlier ingest refill may still read the old block
+    DSR_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (g.dev) hipFree(g.dev);
+    g.dev = nullptr;
+    g.dev_bytes = 0;
+    DSR_CHECK(ctx, hipMalloc(&g.dev, all));
+    g.dev_bytes = all;
+  }
+  return 0;
+}
+
+// Stages every slot (fill[0 .. n) and the empty rest), then uploads the first `stages` staging
+// buffers — desc, t_in, z_in, is_oc, and for host arrays pts, rays, dobs — and `up` bytes of the
+// ingest block, on the context stream: ordered after the previous run's work.
+static int refill_upload(dsr_batch* b, const SlotFill* fill, int n, int stages, size_t up) {
+  dsr_ctx* ctx = b->ctx;
+  auto* desc = static_cast<ObjDesc*>(b->stage[0].host);
+  auto* t_in = static_cast<float*>(b->stage[1].host);
+  auto* z_in = static_cast<float*>(b->stage[2].host);
+  auto* is_oc = static_cast<int*>(b->stage[3].host);
+  for (int o = 0; o < b->n_obj; ++o) {
+    const SlotFill x = o < n ? fill[o] : SlotFill{};
+    ObjDesc d = b->hdesc[o];                       // the slot's offsets; the fill's counts
+    d.n_pts = x.n_pts;
+    d.n_rays = x.n_rays;
+    d.n_fg = x.n_fg;
+    desc[o] = d;
+    float* t = t_in + (size_t)o * 16;
+    for (int i = 0; i < 16; ++i) t[i] = x.pose ? x.pose[i] : (i % 5 == 0 ? 1.f : 0.f);
+    float* z = z_in + (size_t)o * CODE;
+    std::memset(z, 0, sizeof(float) * CODE);
+    if (x.code) std::memcpy(z, x.code, sizeof(float) * b->dec->code_len);
+    is_oc[o] = x.is_oc ? 1 : 0;
+  }
+  hipStream_t s = ctx->stream;
+  for (int k = 0; k < stages; ++k)
+    DSR_CHECK(ctx, hipMemcpyAsync(b->stage[k].dev, b->stage[k].host, b->stage[k].bytes, hipMemcpyHostToDevice, s));
+  if (up) DSR_CHECK(ctx, hipMemcpyAsync(b->ingest.dev, b->ingest.host, up, hipMemcpyHostToDevice, s));
+  return 0;
+}
+
+// The tail of every refill, after the kind's kernels: the one place that says what the batch holds.
+static int refill_end(dsr_batch* b, const dsr_batch::Fill& fill) {
+  dsr_ctx* ctx = b->ctx;
+  hipStream_t s = ctx->stream;
+  // lite flags of the previous fill's rays beyond the new counts are never read, but start clean
+  if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
+  DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
+  b->n_active = fill.shape.n_det;
+  b->last = fill;
+  b->ran = false;
+  return 0;
+}
+
+// The tail of the info entry points: the last fill's records out of the ingest block.
+static int info_download(dsr_batch* b, void* out, const void* recs, size_t bytes) {
+  dsr_ctx* ctx = b->ctx;
+  if (!out) return fail(ctx, "null argument");
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+  DSR_CHECK(ctx, hipMemcpy(out, recs, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- host arrays
 int dsr_batch_refill(dsr_batch* b, int n_obj, const dsr_object_in* in) {
   if (!b) return -2;
   dsr_ctx* ctx = b->ctx;
-  if (!b->capacity) return fail(ctx, "dsr_batch_refill needs a batch from dsr_batch_create_capacity");
+  if (int rc = refill_needs_capacity(b, "refill")) return rc;
   if (n_obj < 0 || n_obj > b->n_obj || (n_obj > 0 && !in))
     return fail(ctx, "refill: n_obj must be in [0, the batch's object capacity]");
   for (int o = 0; o < n_obj; ++o) {
@@ -1702,48 +1900,24 @@ int dsr_batch_refill(dsr_batch* b, int n_obj, const dsr_object_in* in) {
   }
   std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
   hipSetDevice(ctx->device);
-  // the previous refill's copies read the staging buffers until they complete
-  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
-  auto* desc = static_cast<ObjDesc*>(b->stage[0].host);
-  auto* t_in = static_cast<float*>(b->stage[1].host);
-  auto* z_in = static_cast<float*>(b->stage[2].host);
-  auto* is_oc = static_cast<int*>(b->stage[3].host);
+  if (int rc = refill_begin(b, 0, 0)) return rc;
   auto* pts = static_cast<float*>(b->stage[4].host);
   auto* rays = static_cast<float*>(b->stage[5].host);
   auto* dobs = static_cast<float*>(b->stage[6].host);
-  for (int o = 0; o < b->n_obj; ++o) {
-    ObjDesc d = b->hdesc[o];                       // the slot's offsets; the fill's counts
-    const dsr_object_in* x = o < n_obj ? &in[o] : nullptr;
-    d.n_pts = x ? x->n_pts : 0;
-    d.n_rays = x ? x->n_rays : 0;
-    d.n_fg = x ? x->n_depth : 0;
-    desc[o] = d;
-    float* t = t_in + (size_t)o * 16;
-    for (int i = 0; i < 16; ++i) t[i] = x ? x->t_cam_obj[i] : (i % 5 == 0 ? 1.f : 0.f);
-    float* z = z_in + (size_t)o * CODE;
-    std::memset(z, 0, sizeof(float) * CODE);
-    if (x && x->code) std::memcpy(z, x->code, sizeof(float) * b->dec->code_len);
-    is_oc[o] = (x && x->pose_is_obj_cam) ? 1 : 0;
-    if (!x) continue;
-    if (x->n_pts) std::memcpy(pts + (size_t)d.pts_off * 3, x->pts, sizeof(float) * 3 * x->n_pts);
-    if (x->n_rays) std::memcpy(rays + (size_t)d.ray_off * 3, x->rays, sizeof(float) * 3 * x->n_rays);
-    for (int r = 0; r < x->n_rays; ++r) dobs[d.ray_off + r] = r < x->n_depth ? x->depth[r] : 0.f;
+  std::vector<SlotFill> fill(n_obj);
+  for (int o = 0; o < n_obj; ++o) {
+    const dsr_object_in& x = in[o];
+    const ObjDesc& d = b->hdesc[o];
+    fill[o] = SlotFill{x.n_pts, x.n_rays, x.n_depth, x.t_cam_obj, x.code, x.pose_is_obj_cam != 0};
+    if (x.n_pts) std::memcpy(pts + (size_t)d.pts_off * 3, x.pts, sizeof(float) * 3 * x.n_pts);
+    if (x.n_rays) std::memcpy(rays + (size_t)d.ray_off * 3, x.rays, sizeof(float) * 3 * x.n_rays);
+    for (int r = 0; r < x.n_rays; ++r) dobs[d.ray_off + r] = r < x.n_depth ? x.depth[r] : 0.f;
   }
-  hipStream_t s = ctx->stream;                     // ordered after the previous run's work
-  for (const auto& sg : b->stage)
-    DSR_CHECK(ctx, hipMemcpyAsync(sg.dev, sg.host, sg.bytes, hipMemcpyHostToDevice, s));
-  // lite flags of the previous fill's rays beyond the new counts are never read, but start clean
-  if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
-  DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
-  b->n_active = n_obj;
-  b->frame_n = -1;
-  b->frame_pose_pts = -1;
-  b->lidar_shape.n_det = -1;
-  b->ran = false;
-  return 0;
+  if (int rc = refill_upload(b, fill.data(), n_obj, 7, 0)) return rc;
+  return refill_end(b, {dsr_batch::Fill::OBJECTS, LidarShape{0, 3, 0, 0, n_obj}, 0});
 }
 
-// ---- frame ingest (include/dsr.h; kernels and the host rule in dsr_frame.hpp)
+// ---- frame (kernels and the host rule in dsr_frame.hpp)
 int dsr_frame_params_default(dsr_frame_params* p) {
   if (!p) return -2;
   p->max_pts = 250;
@@ -1768,6 +1942,115 @@ int dsr_frame_inputs_host(const dsr_camera* cam, const dsr_frame_params* params,
   return 0;
 }
 
+// the uploaded part of a frame block: depth | instance | detections, laid out as frame_carve does
+static void frame_pack(void* host, const dsr_camera* cam, const float* depth, const int* inst, int n_det,
+                       const dsr_frame_det* dets, const int* modes = nullptr) {
+  const FrameDev H = frame_carve(host, cam->width, cam->height, n_det);
+  const size_t px = (size_t)cam->width * cam->height;
+  std::memcpy(H.depth, depth, px * sizeof(float));
+  std::memcpy(H.inst, inst, px * sizeof(int));
+  for (int d = 0; d < n_det; ++d) {
+    H.dets[d].label = dets[d].label;
+    for (int k = 0; k < 4; ++k) H.dets[d].bbox[k] = dets[d].bbox[k];
+    H.dets[d].mode = modes ? modes[d] : DSR_FRAME_POSE_GIVEN;
+  }
+}
+
+// dsr_frame_inputs (pose_params == null) and dsr_frame_poses: the latter adds k_frame_pose /
+// k_frame_compact, and the given poses travel in a t_in array
+static int frame_call(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params,
+                      const dsr_frame_pose_params* pose_params, const float* depth, const int* instance, int n_det,
+                      const dsr_frame_det* dets, const int* modes, float* pts, float* rays, float* dobs,
+                      dsr_frame_det_out* out, dsr_frame_pose_out* pose_out) {
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const int W = cam->width, H = cam->height;
+  const size_t all = frame_dev_bytes(W, H, n_det) + (pose_params ? frame_pose_dev_bytes(n_det, params->max_pts) : 0);
+  std::vector<char> host(frame_upload_bytes(W, H, n_det));
+  frame_pack(host.data(), cam, depth, instance, n_det, dets, modes);
+  std::vector<float> tin;
+  if (pose_params)
+    for (int d = 0; d < n_det; ++d) tin.insert(tin.end(), dets[d].t_cam_obj, dets[d].t_cam_obj + 16);
+  IngestCall c(ctx, n_det, params->max_pts, params->max_bg, pts, rays, dobs);
+  if (c.upload("frame", host, all, tin)) {
+    const FrameDev D = frame_carve(c.dev, W, H, n_det);
+    const FramePoseDev E = pose_params ? frame_pose_carve(c.dev, W, H, n_det, params->max_pts) : FramePoseDev{};
+    frame_launch(c.s, frame_cam(cam), *params, n_det, D, nullptr, c.d_pts(), c.d_rays(), c.d_dobs());
+    if (pose_params)
+      frame_pose_launch(c.s, *params, *pose_params, n_det, D, E, nullptr, c.d_pts(), c.d_rays(), c.d_dobs(), c.d_tin());
+    c.download("frame kernels");
+    c.records(out, D.recs, sizeof(dsr_frame_det_out) * n_det);
+    if (pose_params) c.records(pose_out, E.precs, sizeof(dsr_frame_pose_out) * n_det);
+  }
+  return c.finish();
+}
+
+int dsr_frame_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params, const float* depth,
+                     const int* instance, int n_det, const dsr_frame_det* dets, float* pts, float* rays,
+                     float* dobs, dsr_frame_det_out* out) {
+  if (!ctx) return -2;
+  if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
+  if (n_det > 0 && (!pts || !rays || !dobs || !out)) return fail(ctx, "frame: null output arrays");
+  if (n_det == 0) return 0;
+  return frame_call(ctx, cam, params, nullptr, depth, instance, n_det, dets, nullptr, pts, rays, dobs, out, nullptr);
+}
+
+// dsr_batch_refill_frame (pose_params == null) and dsr_batch_refill_frame_poses
+static int batch_refill_frame_impl(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                                   const dsr_frame_pose_params* pose_params, const float* depth,
+                                   const int* instance, int n_det, const dsr_frame_det* dets, const int* modes) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  if (int rc = refill_needs_capacity(b, "refill_frame")) return rc;
+  if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
+  if (pose_params)
+    if (const char* m = frame_pose_args_error(pose_params, n_det, modes)) return fail(ctx, m);
+  if (int rc = refill_fits(b, "refill_frame", n_det, params->max_pts, params->max_bg)) return rc;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const int W = cam->width, H = cam->height;
+  const size_t up = frame_upload_bytes(W, H, n_det),
+               all = frame_dev_bytes(W, H, n_det) + (pose_params ? frame_pose_dev_bytes(n_det, params->max_pts) : 0);
+  if (int rc = refill_begin(b, up, all)) return rc;
+  frame_pack(b->ingest.host, cam, depth, instance, n_det, dets, pose_params ? modes : nullptr);
+  std::vector<SlotFill> fill(n_det);                // k_frame_scan writes the counts
+  for (int o = 0; o < n_det; ++o) {
+    // a cuboid detection's pose row is written by k_frame_pose after this upload (t_cam_obj)
+    const bool given = !(pose_params && modes[o] != DSR_FRAME_POSE_GIVEN);
+    fill[o].pose = given ? dets[o].t_cam_obj : nullptr;
+    fill[o].code = dets[o].code;
+    fill[o].is_oc = given && dets[o].pose_is_obj_cam;
+  }
+  if (int rc = refill_upload(b, fill.data(), n_det, 4, up)) return rc;   // (pts / rays / dobs: the kernels)
+  if (n_det > 0) {
+    const FrameDev D = frame_carve(b->ingest.dev, W, H, n_det);
+    frame_launch(ctx->stream, frame_cam(cam), *params, n_det, D, b->desc, b->pts, b->rays, b->dobs);
+    if (pose_params)
+      frame_pose_launch(ctx->stream, *params, *pose_params, n_det, D,
+                        frame_pose_carve(b->ingest.dev, W, H, n_det, params->max_pts), b->desc, b->pts, b->rays,
+                        b->dobs, b->t_in);
+    DSR_CHECK(ctx, hipGetLastError());
+  }
+  return refill_end(b, {pose_params ? dsr_batch::Fill::FRAME_POSES : dsr_batch::Fill::FRAME,
+                        LidarShape{0, 3, W, H, n_det}, params->max_pts});
+}
+
+int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
+                           const float* depth, const int* instance, int n_det, const dsr_frame_det* dets) {
+  return batch_refill_frame_impl(b, cam, params, nullptr, depth, instance, n_det, dets, nullptr);
+}
+
+int dsr_batch_frame_info(dsr_batch* b, dsr_frame_det_out* out) {
+  if (!b) return -2;
+  const dsr_batch::Fill& f = b->last;
+  if (f.kind != dsr_batch::Fill::FRAME && f.kind != dsr_batch::Fill::FRAME_POSES)
+    return fail(b->ctx, "dsr_batch_frame_info: the batch's last fill was not a frame (dsr_batch_refill_frame)");
+  if (f.shape.n_det == 0) return 0;
+  const FrameDev D = frame_carve(b->ingest.dev, f.shape.W, f.shape.H, f.shape.n_det);
+  return info_download(b, out, D.recs, sizeof(dsr_frame_det_out) * f.shape.n_det);
+}
+
+// ---- frame with start poses
 int dsr_frame_pose_params_default(dsr_frame_pose_params* p) {
   if (!p) return -2;
   p->outlier_radius = 1.0f;
@@ -1794,151 +2077,6 @@ int dsr_frame_poses_host(const dsr_camera* cam, const dsr_frame_params* params,
   return 0;
 }
 
-// the uploaded part of a frame block: depth | instance | detections, laid out as frame_carve does
-static void frame_pack(void* host, const dsr_camera* cam, const float* depth, const int* inst, int n_det,
-                       const dsr_frame_det* dets, const int* modes = nullptr) {
-  const FrameDev H = frame_carve(host, cam->width, cam->height, n_det);
-  const size_t px = (size_t)cam->width * cam->height;
-  std::memcpy(H.depth, depth, px * sizeof(float));
-  std::memcpy(H.inst, inst, px * sizeof(int));
-  for (int d = 0; d < n_det; ++d) {
-    H.dets[d].label = dets[d].label;
-    for (int k = 0; k < 4; ++k) H.dets[d].bbox[k] = dets[d].bbox[k];
-    H.dets[d].mode = modes ? modes[d] : DSR_FRAME_POSE_GIVEN;
-  }
-}
-
-int dsr_frame_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params, const float* depth,
-                     const int* instance, int n_det, const dsr_frame_det* dets, float* pts, float* rays,
-                     float* dobs, dsr_frame_det_out* out) {
-  if (!ctx) return -2;
-  if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
-  if (n_det > 0 && (!pts || !rays || !dobs || !out)) return fail(ctx, "frame: null output arrays");
-  if (n_det == 0) return 0;
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  const int W = cam->width, H = cam->height;
-  const size_t up = frame_upload_bytes(W, H, n_det), all = frame_dev_bytes(W, H, n_det);
-  const size_t np = (size_t)n_det * params->max_pts * 3, nr = (size_t)n_det * ((size_t)params->max_pts + params->max_bg) * 3,
-               nz = (size_t)n_det * params->max_pts;
-  std::vector<char> host(up);
-  frame_pack(host.data(), cam, depth, instance, n_det, dets);
-  char* dev = nullptr;
-  float* o = nullptr;                            // pts | rays | dobs
-  hipStream_t s = ctx->stream;
-  int rc = 0;
-  auto chk = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == 0) {
-      ctx->err = std::string(what) + ": " + hipGetErrorString(e);
-      rc = -1;
-    }
-    return e == hipSuccess;
-  };
-  if (chk(hipMalloc((void**)&dev, all), "hipMalloc (frame)") &&
-      chk(hipMalloc((void**)&o, sizeof(float) * (np + nr + nz)), "hipMalloc (frame outputs)")) {
-    const FrameDev D = frame_carve(dev, W, H, n_det);
-    // rows beyond a detection's counts come back as the caller had them
-    chk(hipMemcpyAsync(dev, host.data(), up, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o, pts, sizeof(float) * np, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o + np, rays, sizeof(float) * nr, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o + np + nr, dobs, sizeof(float) * nz, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    if (rc == 0) {
-      frame_launch(s, frame_cam(cam), *params, n_det, D, nullptr, o, o + np, o + np + nr);
-      chk(hipGetLastError(), "frame kernels");
-      chk(hipMemcpyAsync(pts, o, sizeof(float) * np, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(rays, o + np, sizeof(float) * nr, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(dobs, o + np + nr, sizeof(float) * nz, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(out, D.recs, sizeof(dsr_frame_det_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-    }
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-  }
-  if (o) hipFree(o);
-  if (dev) hipFree(dev);
-  return rc;
-}
-
-// dsr_batch_refill_frame (pose_params == null) and dsr_batch_refill_frame_poses
-static int batch_refill_frame_impl(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
-                                   const dsr_frame_pose_params* pose_params, const float* depth,
-                                   const int* instance, int n_det, const dsr_frame_det* dets, const int* modes) {
-  if (!b) return -2;
-  dsr_ctx* ctx = b->ctx;
-  if (!b->capacity) return fail(ctx, "dsr_batch_refill_frame needs a batch from dsr_batch_create_capacity");
-  if (const char* m = frame_args_error(cam, params, depth, instance, n_det, dets)) return fail(ctx, m);
-  if (pose_params)
-    if (const char* m = frame_pose_args_error(pose_params, n_det, modes)) return fail(ctx, m);
-  if (n_det > b->n_obj) return fail(ctx, "refill_frame: n_det exceeds the batch's object capacity");
-  if (params->max_pts > b->max_pts) return fail(ctx, "refill_frame: max_pts exceeds the batch's max_pts");
-  if ((long long)params->max_pts + params->max_bg > b->max_rays)
-    return fail(ctx, "refill_frame: max_pts + max_bg exceeds the batch's max_rays");
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  // the previous refill's copies read the staging buffers until they complete
-  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
-  const int W = cam->width, H = cam->height;
-  const size_t up = frame_upload_bytes(W, H, n_det),
-               all = frame_dev_bytes(W, H, n_det) + (pose_params ? frame_pose_dev_bytes(n_det, params->max_pts) : 0);
-  hipStream_t s = ctx->stream;
-  if (up > b->frame_host_bytes) {
-    if (b->frame_host) hipHostFree(b->frame_host);
-    b->frame_host = nullptr;
-    b->frame_host_bytes = 0;
-    DSR_CHECK(ctx, hipHostMalloc(&b->frame_host, up, hipHostMallocDefault));
-    b->frame_host_bytes = up;
-  }
-  if (all > b->frame_dev_bytes) {
-    // the kernels of an earlier frame refill may still read the old block
-    DSR_CHECK(ctx, hipStreamSynchronize(s));
-    if (b->frame_dev) hipFree(b->frame_dev);
-    b->frame_dev = nullptr;
-    b->frame_dev_bytes = 0;
-    DSR_CHECK(ctx, hipMalloc(&b->frame_dev, all));
-    b->frame_dev_bytes = all;
-  }
-  frame_pack(b->frame_host, cam, depth, instance, n_det, dets, pose_params ? modes : nullptr);
-  auto* desc = static_cast<ObjDesc*>(b->stage[0].host);
-  auto* t_in = static_cast<float*>(b->stage[1].host);
-  auto* z_in = static_cast<float*>(b->stage[2].host);
-  auto* is_oc = static_cast<int*>(b->stage[3].host);
-  for (int o = 0; o < b->n_obj; ++o) {
-    ObjDesc d = b->hdesc[o];                       // the slot's offsets; k_frame_scan writes the counts
-    d.n_pts = d.n_rays = d.n_fg = 0;
-    desc[o] = d;
-    const dsr_frame_det* x = o < n_det ? &dets[o] : nullptr;
-    // a cuboid detection's pose row is written by k_frame_pose after this upload (t_cam_obj)
-    const bool given = x && !(pose_params && modes[o] != DSR_FRAME_POSE_GIVEN);
-    float* t = t_in + (size_t)o * 16;
-    for (int i = 0; i < 16; ++i) t[i] = given ? x->t_cam_obj[i] : (i % 5 == 0 ? 1.f : 0.f);
-    float* z = z_in + (size_t)o * CODE;
-    std::memset(z, 0, sizeof(float) * CODE);
-    if (x && x->code) std::memcpy(z, x->code, sizeof(float) * b->dec->code_len);
-    is_oc[o] = (given && x->pose_is_obj_cam) ? 1 : 0;
-  }
-  for (int k = 0; k < 4; ++k)                      // desc, t_in, z_in, is_oc (pts / rays / dobs: the kernels)
-    DSR_CHECK(ctx, hipMemcpyAsync(b->stage[k].dev, b->stage[k].host, b->stage[k].bytes, hipMemcpyHostToDevice, s));
-  DSR_CHECK(ctx, hipMemcpyAsync(b->frame_dev, b->frame_host, up, hipMemcpyHostToDevice, s));
-  if (n_det > 0) {
-    const FrameDev D = frame_carve(b->frame_dev, W, H, n_det);
-    frame_launch(s, frame_cam(cam), *params, n_det, D, b->desc, b->pts, b->rays, b->dobs);
-    if (pose_params)
-      frame_pose_launch(s, *params, *pose_params, n_det, D,
-                        frame_pose_carve(b->frame_dev, W, H, n_det, params->max_pts), b->desc, b->pts, b->rays,
-                        b->dobs, b->t_in);
-    DSR_CHECK(ctx, hipGetLastError());
-  }
-  if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
-  DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
-  b->n_active = n_det;
-  b->frame_n = n_det;
-  b->frame_w = W;
-  b->frame_h = H;
-  b->frame_pose_pts = pose_params ? params->max_pts : -1;
-  b->lidar_shape.n_det = -1;
-  b->ran = false;
-  return 0;
-}
-
-// dsr_frame_inputs plus k_frame_pose / k_frame_compact; the given poses travel in a t_in array
 int dsr_frame_poses(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params* params,
                     const dsr_frame_pose_params* pose_params, const float* depth, const int* instance,
                     int n_det, const dsr_frame_det* dets, const int* modes, float* pts, float* rays,
@@ -1948,58 +2086,7 @@ int dsr_frame_poses(dsr_ctx* ctx, const dsr_camera* cam, const dsr_frame_params*
   if (const char* m = frame_pose_args_error(pose_params, n_det, modes)) return fail(ctx, m);
   if (n_det > 0 && (!pts || !rays || !dobs || !out || !pose_out)) return fail(ctx, "frame: null output arrays");
   if (n_det == 0) return 0;
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  const int W = cam->width, H = cam->height;
-  const size_t up = frame_upload_bytes(W, H, n_det),
-               all = frame_dev_bytes(W, H, n_det) + frame_pose_dev_bytes(n_det, params->max_pts);
-  const size_t np = (size_t)n_det * params->max_pts * 3, nr = (size_t)n_det * ((size_t)params->max_pts + params->max_bg) * 3,
-               nz = (size_t)n_det * params->max_pts, nt = (size_t)n_det * 16;
-  std::vector<char> host(up);
-  frame_pack(host.data(), cam, depth, instance, n_det, dets, modes);
-  std::vector<float> tin(nt);
-  for (int d = 0; d < n_det; ++d)
-    for (int i = 0; i < 16; ++i) tin[(size_t)d * 16 + i] = dets[d].t_cam_obj[i];
-  char* dev = nullptr;
-  float* o = nullptr;                            // pts | rays | dobs | t_in
-  hipStream_t s = ctx->stream;
-  int rc = 0;
-  auto chk = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == 0) {
-      ctx->err = std::string(what) + ": " + hipGetErrorString(e);
-      rc = -1;
-    }
-    return e == hipSuccess;
-  };
-  if (chk(hipMalloc((void**)&dev, all), "hipMalloc (frame)") &&
-      chk(hipMalloc((void**)&o, sizeof(float) * (np + nr + nz + nt)), "hipMalloc (frame outputs)")) {
-    const FrameDev D = frame_carve(dev, W, H, n_det);
-    const FramePoseDev E = frame_pose_carve(dev, W, H, n_det, params->max_pts);
-    chk(hipMemcpyAsync(dev, host.data(), up, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o, pts, sizeof(float) * np, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o + np, rays, sizeof(float) * nr, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o + np + nr, dobs, sizeof(float) * nz, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o + np + nr + nz, tin.data(), sizeof(float) * nt, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    if (rc == 0) {
-      frame_launch(s, frame_cam(cam), *params, n_det, D, nullptr, o, o + np, o + np + nr);
-      frame_pose_launch(s, *params, *pose_params, n_det, D, E, nullptr, o, o + np, o + np + nr, o + np + nr + nz);
-      chk(hipGetLastError(), "frame kernels");
-      chk(hipMemcpyAsync(pts, o, sizeof(float) * np, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(rays, o + np, sizeof(float) * nr, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(dobs, o + np + nr, sizeof(float) * nz, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(out, D.recs, sizeof(dsr_frame_det_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(pose_out, E.precs, sizeof(dsr_frame_pose_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-    }
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-  }
-  if (o) hipFree(o);
-  if (dev) hipFree(dev);
-  return rc;
-}
-
-int dsr_batch_refill_frame(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
-                           const float* depth, const int* instance, int n_det, const dsr_frame_det* dets) {
-  return batch_refill_frame_impl(b, cam, params, nullptr, depth, instance, n_det, dets, nullptr);
+  return frame_call(ctx, cam, params, pose_params, depth, instance, n_det, dets, modes, pts, rays, dobs, out, pose_out);
 }
 
 int dsr_batch_refill_frame_poses(dsr_batch* b, const dsr_camera* cam, const dsr_frame_params* params,
@@ -2012,31 +2099,113 @@ int dsr_batch_refill_frame_poses(dsr_batch* b, const dsr_camera* cam, const dsr_
 
 int dsr_batch_frame_pose_info(dsr_batch* b, dsr_frame_pose_out* out) {
   if (!b) return -2;
-  dsr_ctx* ctx = b->ctx;
-  if (b->frame_n < 0 || b->frame_pose_pts < 0)
-    return fail(ctx, "dsr_batch_frame_pose_info: the batch's last fill was not a frame with poses (dsr_batch_refill_frame_poses)");
-  if (b->frame_n == 0) return 0;
-  if (!out) return fail(ctx, "null argument");
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
-  const FramePoseDev E = frame_pose_carve(b->frame_dev, b->frame_w, b->frame_h, b->frame_n, b->frame_pose_pts);
-  DSR_CHECK(ctx, hipMemcpy(out, E.precs, sizeof(dsr_frame_pose_out) * b->frame_n, hipMemcpyDeviceToHost));
+  const dsr_batch::Fill& f = b->last;
+  if (f.kind != dsr_batch::Fill::FRAME_POSES)
+    return fail(b->ctx, "dsr_batch_frame_pose_info: the batch's last fill was not a frame with poses (dsr_batch_refill_frame_poses)");
+  if (f.shape.n_det == 0) return 0;
+  const FramePoseDev E = frame_pose_carve(b->ingest.dev, f.shape.W, f.shape.H, f.shape.n_det, f.max_pts);
+  return info_download(b, out, E.precs, sizeof(dsr_frame_pose_out) * f.shape.n_det);
+}
+
+// ---- LiDAR sweep (kernels and the host rule in dsr_lidar.hpp)
+int dsr_lidar_params_default(dsr_lidar_params* p) {
+  if (!p) return -2;
+  p->max_pts = 250;
+  p->max_bg = 200;
+  p->downsample = 4;
+  p->expand = 5;
+  p->min_mask_area = 1000;
+  p->radius = 3.0f;
+  p->box_margin = 1.1f;
   return 0;
 }
 
-int dsr_batch_frame_info(dsr_batch* b, dsr_frame_det_out* out) {
-  if (!b) return -2;
-  dsr_ctx* ctx = b->ctx;
-  if (b->frame_n < 0) return fail(ctx, "dsr_batch_frame_info: the batch's last fill was not a frame (dsr_batch_refill_frame)");
-  if (b->frame_n == 0) return 0;
-  if (!out) return fail(ctx, "null argument");
+// t_cam_velo is validated as dsr_reconstruct_views validates t_view_ref
+static bool lidar_rigid(const float* t) {
+  float inv[16];
+  return t && rigid_inverse(t, inv);
+}
+
+static LidarShape lidar_shape(const dsr_camera* cam, int n_velo, int stride, int n_det) {
+  return LidarShape{n_velo, stride, cam->width, cam->height, n_det};
+}
+
+int dsr_lidar_inputs_host(const dsr_camera* cam, const dsr_lidar_params* params, const float* t_cam_velo,
+                          const float* velo, int n_velo, int stride, const int* instance, int n_masks,
+                          const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
+                          float* rays, float* dobs, dsr_lidar_det_out* out) {
+  if (lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks, masks, n_det, dets))
+    return -2;
+  lidar_inputs_host_impl(frame_cam(cam), *params, t_cam_velo, velo, n_velo, stride, instance, n_masks, masks, n_det,
+                         dets, pts, rays, dobs, out);
+  return 0;
+}
+
+int dsr_lidar_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_lidar_params* params,
+                     const float* t_cam_velo, const float* velo, int n_velo, int stride, const int* instance,
+                     int n_masks, const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
+                     float* rays, float* dobs, dsr_lidar_det_out* out) {
+  if (!ctx) return -2;
+  if (const char* m = lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks,
+                                       masks, n_det, dets))
+    return fail(ctx, m);
+  if (n_det > 0 && (!pts || !rays || !dobs || !out)) return fail(ctx, "lidar: null output arrays");
+  if (n_det == 0) return 0;
   std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
   hipSetDevice(ctx->device);
-  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
-  const FrameDev D = frame_carve(b->frame_dev, b->frame_w, b->frame_h, b->frame_n);
-  DSR_CHECK(ctx, hipMemcpy(out, D.recs, sizeof(dsr_frame_det_out) * b->frame_n, hipMemcpyDeviceToHost));
-  return 0;
+  const LidarShape S = lidar_shape(cam, n_velo, stride, n_det);
+  std::vector<char> host(lidar_upload_bytes(S));
+  lidar_pack(host.data(), S, *params, t_cam_velo, velo, instance, n_masks, masks, dets);
+  IngestCall c(ctx, n_det, params->max_pts, params->max_bg, pts, rays, dobs);
+  if (c.upload("lidar", host, lidar_dev_bytes(S))) {
+    const LidarDev D = lidar_carve(c.dev, S);
+    lidar_launch(c.s, frame_cam(cam), *params, lidar_xf(t_cam_velo), S, n_masks, D, nullptr, c.d_pts(), c.d_rays(),
+                 c.d_dobs());
+    c.download("lidar kernels");
+    c.records(out, D.recs, sizeof(dsr_lidar_det_out) * n_det);
+  }
+  return c.finish();
+}
+
+int dsr_batch_refill_lidar(dsr_batch* b, const dsr_camera* cam, const dsr_lidar_params* params,
+                           const float* t_cam_velo, const float* velo, int n_velo, int stride,
+                           const int* instance, int n_masks, const dsr_lidar_mask* masks, int n_det,
+                           const dsr_lidar_det* dets) {
+  if (!b) return -2;
+  dsr_ctx* ctx = b->ctx;
+  if (int rc = refill_needs_capacity(b, "refill_lidar")) return rc;
+  if (const char* m = lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks,
+                                       masks, n_det, dets))
+    return fail(ctx, m);
+  if (int rc = refill_fits(b, "refill_lidar", n_det, params->max_pts, params->max_bg)) return rc;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const LidarShape S = lidar_shape(cam, n_velo, stride, n_det);
+  const size_t up = lidar_upload_bytes(S);
+  if (int rc = refill_begin(b, up, lidar_dev_bytes(S))) return rc;
+  lidar_pack(b->ingest.host, S, *params, t_cam_velo, velo, instance, n_masks, masks, dets);
+  const LidarDev Hd = lidar_carve(b->ingest.host, S);
+  std::vector<SlotFill> fill(n_det);                // k_lidar_bg_scan writes the counts
+  for (int o = 0; o < n_det; ++o) {
+    fill[o].pose = Hd.dets[o].tco;
+    fill[o].code = dets[o].code;
+  }
+  if (int rc = refill_upload(b, fill.data(), n_det, 4, up)) return rc;   // (pts / rays / dobs: the kernels)
+  if (n_det > 0) {
+    lidar_launch(ctx->stream, frame_cam(cam), *params, lidar_xf(t_cam_velo), S, n_masks, lidar_carve(b->ingest.dev, S),
+                 b->desc, b->pts, b->rays, b->dobs);
+    DSR_CHECK(ctx, hipGetLastError());
+  }
+  return refill_end(b, {dsr_batch::Fill::SWEEP, S, 0});
+}
+
+int dsr_batch_lidar_info(dsr_batch* b, dsr_lidar_det_out* out) {
+  if (!b) return -2;
+  const dsr_batch::Fill& f = b->last;
+  if (f.kind != dsr_batch::Fill::SWEEP)
+    return fail(b->ctx, "dsr_batch_lidar_info: the batch's last fill was not a sweep (dsr_batch_refill_lidar)");
+  if (f.shape.n_det == 0) return 0;
+  return info_download(b, out, lidar_carve(b->ingest.dev, f.shape).recs, sizeof(dsr_lidar_det_out) * f.shape.n_det);
 }
 
 static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
@@ -2723,34 +2892,6 @@ int dsr_reconstruct_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_
   return rc;
 }
 
-// inverse of a rigid 4x4 (x_view = t_view_ref x_ref) in fp64, rounded once: [R^T | -R^T t].
-// False unless the last row is 0 0 0 1 and R^T R = I within 1e-4 with det R > 0.
-static bool rigid_inverse(const float* t, float* out) {
-  if (t[12] != 0.f || t[13] != 0.f || t[14] != 0.f || t[15] != 1.f) return false;
-  double R[3][3], tr[3];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) R[i][j] = (double)t[i * 4 + j];
-    tr[i] = (double)t[i * 4 + 3];
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double s = 0.0;
-      for (int k = 0; k < 3; ++k) s += R[k][i] * R[k][j];
-      if (!(std::fabs(s - (i == j ? 1.0 : 0.0)) <= 1e-4)) return false;       // (NaN fails too)
-    }
-  const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
-                     R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
-  if (!(det > 0.0)) return false;
-  for (int i = 0; i < 3; ++i) {
-    if (!std::isfinite(tr[i])) return false;
-    for (int j = 0; j < 3; ++j) out[i * 4 + j] = (float)R[j][i];
-    out[i * 4 + 3] = (float)(-(R[0][i] * tr[0] + R[1][i] * tr[1] + R[2][i] * tr[2]));
-  }
-  out[12] = out[13] = out[14] = 0.f;
-  out[15] = 1.f;
-  return true;
-}
-
 int dsr_reconstruct_views(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p, int n_obj,
                           const dsr_views_object_in* in, dsr_object_out* out, const dsr_trace* trace,
                           int* fail_view, dsr_stats* stats) {
@@ -2813,180 +2954,6 @@ int dsr_reconstruct_views(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_
   if (!rc && stats) rc = dsr_batch_stats(b, stats);
   dsr_batch_destroy(b);
   return rc;
-}
-
-// ---- LiDAR keyframe ingest (include/dsr.h; kernels and the host rule in dsr_lidar.hpp)
-int dsr_lidar_params_default(dsr_lidar_params* p) {
-  if (!p) return -2;
-  p->max_pts = 250;
-  p->max_bg = 200;
-  p->downsample = 4;
-  p->expand = 5;
-  p->min_mask_area = 1000;
-  p->radius = 3.0f;
-  p->box_margin = 1.1f;
-  return 0;
-}
-
-// t_cam_velo is validated as dsr_reconstruct_views validates t_view_ref
-static bool lidar_rigid(const float* t) {
-  float inv[16];
-  return t && rigid_inverse(t, inv);
-}
-
-static LidarShape lidar_shape(const dsr_camera* cam, int n_velo, int stride, int n_det) {
-  return LidarShape{n_velo, stride, cam->width, cam->height, n_det};
-}
-
-int dsr_lidar_inputs_host(const dsr_camera* cam, const dsr_lidar_params* params, const float* t_cam_velo,
-                          const float* velo, int n_velo, int stride, const int* instance, int n_masks,
-                          const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
-                          float* rays, float* dobs, dsr_lidar_det_out* out) {
-  if (lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks, masks, n_det, dets))
-    return -2;
-  lidar_inputs_host_impl(frame_cam(cam), *params, t_cam_velo, velo, n_velo, stride, instance, n_masks, masks, n_det,
-                         dets, pts, rays, dobs, out);
-  return 0;
-}
-
-int dsr_lidar_inputs(dsr_ctx* ctx, const dsr_camera* cam, const dsr_lidar_params* params,
-                     const float* t_cam_velo, const float* velo, int n_velo, int stride, const int* instance,
-                     int n_masks, const dsr_lidar_mask* masks, int n_det, const dsr_lidar_det* dets, float* pts,
-                     float* rays, float* dobs, dsr_lidar_det_out* out) {
-  if (!ctx) return -2;
-  if (const char* m = lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks,
-                                       masks, n_det, dets))
-    return fail(ctx, m);
-  if (n_det > 0 && (!pts || !rays || !dobs || !out)) return fail(ctx, "lidar: null output arrays");
-  if (n_det == 0) return 0;
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  const LidarShape S = lidar_shape(cam, n_velo, stride, n_det);
-  const size_t up = lidar_upload_bytes(S), all = lidar_dev_bytes(S);
-  const size_t np = (size_t)n_det * params->max_pts * 3, nr = (size_t)n_det * ((size_t)params->max_pts + params->max_bg) * 3,
-               nz = (size_t)n_det * params->max_pts;
-  std::vector<char> host(up);
-  lidar_pack(host.data(), S, *params, t_cam_velo, velo, instance, n_masks, masks, dets);
-  char* dev = nullptr;
-  float* o = nullptr;                            // pts | rays | dobs
-  hipStream_t s = ctx->stream;
-  int rc = 0;
-  auto chk = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == 0) {
-      ctx->err = std::string(what) + ": " + hipGetErrorString(e);
-      rc = -1;
-    }
-    return e == hipSuccess;
-  };
-  if (chk(hipMalloc((void**)&dev, all), "hipMalloc (lidar)") &&
-      chk(hipMalloc((void**)&o, sizeof(float) * (np + nr + nz)), "hipMalloc (lidar outputs)")) {
-    const LidarDev D = lidar_carve(dev, S);
-    // rows beyond a detection's counts come back as the caller had them
-    chk(hipMemcpyAsync(dev, host.data(), up, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o, pts, sizeof(float) * np, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o + np, rays, sizeof(float) * nr, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    chk(hipMemcpyAsync(o + np + nr, dobs, sizeof(float) * nz, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-    if (rc == 0) {
-      lidar_launch(s, frame_cam(cam), *params, lidar_xf(t_cam_velo), S, n_masks, D, nullptr, o, o + np, o + np + nr);
-      chk(hipGetLastError(), "lidar kernels");
-      chk(hipMemcpyAsync(pts, o, sizeof(float) * np, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(rays, o + np, sizeof(float) * nr, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(dobs, o + np + nr, sizeof(float) * nz, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-      chk(hipMemcpyAsync(out, D.recs, sizeof(dsr_lidar_det_out) * n_det, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-    }
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-  }
-  if (o) hipFree(o);
-  if (dev) hipFree(dev);
-  return rc;
-}
-
-int dsr_batch_refill_lidar(dsr_batch* b, const dsr_camera* cam, const dsr_lidar_params* params,
-                           const float* t_cam_velo, const float* velo, int n_velo, int stride,
-                           const int* instance, int n_masks, const dsr_lidar_mask* masks, int n_det,
-                           const dsr_lidar_det* dets) {
-  if (!b) return -2;
-  dsr_ctx* ctx = b->ctx;
-  if (!b->capacity) return fail(ctx, "dsr_batch_refill_lidar needs a batch from dsr_batch_create_capacity");
-  if (const char* m = lidar_args_error(cam, params, lidar_rigid(t_cam_velo), velo, n_velo, stride, instance, n_masks,
-                                       masks, n_det, dets))
-    return fail(ctx, m);
-  if (n_det > b->n_obj) return fail(ctx, "refill_lidar: n_det exceeds the batch's object capacity");
-  if (params->max_pts > b->max_pts) return fail(ctx, "refill_lidar: max_pts exceeds the batch's max_pts");
-  if ((long long)params->max_pts + params->max_bg > b->max_rays)
-    return fail(ctx, "refill_lidar: max_pts + max_bg exceeds the batch's max_rays");
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  // the previous refill's copies read the staging buffers until they complete
-  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
-  const LidarShape S = lidar_shape(cam, n_velo, stride, n_det);
-  const size_t up = lidar_upload_bytes(S), all = lidar_dev_bytes(S);
-  hipStream_t s = ctx->stream;
-  if (up > b->lidar_host_bytes) {
-    if (b->lidar_host) hipHostFree(b->lidar_host);
-    b->lidar_host = nullptr;
-    b->lidar_host_bytes = 0;
-    DSR_CHECK(ctx, hipHostMalloc(&b->lidar_host, up, hipHostMallocDefault));
-    b->lidar_host_bytes = up;
-  }
-  if (all > b->lidar_dev_bytes) {
-    // the kernels of an earlier sweep refill may still read the old block
-    DSR_CHECK(ctx, hipStreamSynchronize(s));
-    if (b->lidar_dev) hipFree(b->lidar_dev);
-    b->lidar_dev = nullptr;
-    b->lidar_dev_bytes = 0;
-    DSR_CHECK(ctx, hipMalloc(&b->lidar_dev, all));
-    b->lidar_dev_bytes = all;
-  }
-  lidar_pack(b->lidar_host, S, *params, t_cam_velo, velo, instance, n_masks, masks, dets);
-  const LidarDev Hd = lidar_carve(b->lidar_host, S);
-  auto* desc = static_cast<ObjDesc*>(b->stage[0].host);
-  auto* t_in = static_cast<float*>(b->stage[1].host);
-  auto* z_in = static_cast<float*>(b->stage[2].host);
-  auto* is_oc = static_cast<int*>(b->stage[3].host);
-  for (int o = 0; o < b->n_obj; ++o) {
-    ObjDesc d = b->hdesc[o];                       // the slot's offsets; k_lidar_bg_scan writes the counts
-    d.n_pts = d.n_rays = d.n_fg = 0;
-    desc[o] = d;
-    const dsr_lidar_det* x = o < n_det ? &dets[o] : nullptr;
-    float* t = t_in + (size_t)o * 16;
-    for (int i = 0; i < 16; ++i) t[i] = x ? Hd.dets[o].tco[i] : (i % 5 == 0 ? 1.f : 0.f);
-    float* z = z_in + (size_t)o * CODE;
-    std::memset(z, 0, sizeof(float) * CODE);
-    if (x && x->code) std::memcpy(z, x->code, sizeof(float) * b->dec->code_len);
-    is_oc[o] = 0;
-  }
-  for (int k = 0; k < 4; ++k)                      // desc, t_in, z_in, is_oc (pts / rays / dobs: the kernels)
-    DSR_CHECK(ctx, hipMemcpyAsync(b->stage[k].dev, b->stage[k].host, b->stage[k].bytes, hipMemcpyHostToDevice, s));
-  DSR_CHECK(ctx, hipMemcpyAsync(b->lidar_dev, b->lidar_host, up, hipMemcpyHostToDevice, s));
-  if (n_det > 0) {
-    lidar_launch(s, frame_cam(cam), *params, lidar_xf(t_cam_velo), S, n_masks, lidar_carve(b->lidar_dev, S), b->desc,
-                 b->pts, b->rays, b->dobs);
-    DSR_CHECK(ctx, hipGetLastError());
-  }
-  if (b->refine) DSR_CHECK(ctx, hipMemsetAsync(b->refine, 0, (size_t)std::max(1, b->cand_total), s));
-  DSR_CHECK(ctx, hipEventRecord(b->up_ev, s));
-  b->n_active = n_det;
-  b->frame_n = -1;
-  b->frame_pose_pts = -1;
-  b->lidar_shape = S;
-  b->ran = false;
-  return 0;
-}
-
-int dsr_batch_lidar_info(dsr_batch* b, dsr_lidar_det_out* out) {
-  if (!b) return -2;
-  dsr_ctx* ctx = b->ctx;
-  if (b->lidar_shape.n_det < 0)
-    return fail(ctx, "dsr_batch_lidar_info: the batch's last fill was not a sweep (dsr_batch_refill_lidar)");
-  if (b->lidar_shape.n_det == 0) return 0;
-  if (!out) return fail(ctx, "null argument");
-  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
-  hipSetDevice(ctx->device);
-  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
-  const LidarDev D = lidar_carve(b->lidar_dev, b->lidar_shape);
-  DSR_CHECK(ctx, hipMemcpy(out, D.recs, sizeof(dsr_lidar_det_out) * b->lidar_shape.n_det, hipMemcpyDeviceToHost));
-  return 0;
 }
 
 // ------------------------------------------------------------------------------------

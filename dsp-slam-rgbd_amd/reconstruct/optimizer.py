@@ -363,37 +363,51 @@ class Optimizer(object):
                 res.append(r)
             return self._mesh_results(res, mesher)
         dets, keep = U.frame_dets([U._with_pose(h) for h in hyp], self.code_len)
-        outs = (L.ObjectOut * n)()
-        recs = (L.FrameDetOut * n)()
-        precs = (L.FramePoseOut * n)()
+        infos = [("dsr_batch_frame_info", L.FrameDetOut)]
         if poses:
             modes = U.frame_pose_modes(hyp)
             ctx.check(ctx.lib.dsr_batch_refill_frame_poses(slot.handle, cam, p, q, L.fptr(depth), L.iptr(instance), n,
                                                            dets, L.iptr(modes)), "dsr_batch_refill_frame_poses")
+            infos.append(("dsr_batch_frame_pose_info", L.FramePoseOut))
         else:
             ctx.check(ctx.lib.dsr_batch_refill_frame(slot.handle, cam, p, L.fptr(depth), L.iptr(instance), n, dets),
                       "dsr_batch_refill_frame")
-        slot.busy = True
-        try:
-            ctx.check(ctx.lib.dsr_batch_run(slot.handle), "dsr_batch_run")
-            ctx.check(ctx.lib.dsr_batch_download(slot.handle, outs), "dsr_batch_download")
-            ctx.check(ctx.lib.dsr_batch_frame_info(slot.handle, recs), "dsr_batch_frame_info")
-            if poses:
-                ctx.check(ctx.lib.dsr_batch_frame_pose_info(slot.handle, precs), "dsr_batch_frame_pose_info")
-        finally:
-            slot.busy = False
+        outs, recs, result = self._run_slot(slot, n, infos)
         res = []
         for i, j in pairs:
             k = i
             if j is not None and float(outs[i].loss) > float(outs[j].loss):
                 k = j
-            r = self._result(outs[k], self.code_len)
-            r["iters_done"] = int(outs[k].iters_done)
-            r["fail_reason"] = L.FAIL_REASONS.get(int(outs[k].fail_reason), "?")
-            r["ingest"] = U.frame_record(recs[k])
-            r["pose_init"] = U.frame_pose_record(precs[k]) if poses else given_record(hyp[k], r["ingest"])
-            res.append(r)
+            ingest = U.frame_record(recs[0][k])
+            res.append(result(k, ingest=ingest, pose_init=(U.frame_pose_record(recs[1][k]) if poses
+                                                            else given_record(hyp[k], ingest))))
         return self._mesh_results(res, mesher)
+
+    def _run_slot(self, slot, n, infos):
+        """The slot sequence after a refill of ``n`` objects: mark the slot busy, run, download the
+        out-records, fetch the fill's info records (``infos``: (entry point, record type) pairs) and
+        release the slot.  Returns the out-records, one record array per entry of ``infos``, and
+        ``result(k, **more)``: out-record k as a result dict with ``iters_done``, ``fail_reason``
+        and ``more``."""
+        ctx = self._ctx
+        outs = (L.ObjectOut * n)()
+        recs = [(rtype * n)() for _, rtype in infos]
+        slot.busy = True
+        try:
+            ctx.check(ctx.lib.dsr_batch_run(slot.handle), "dsr_batch_run")
+            ctx.check(ctx.lib.dsr_batch_download(slot.handle, outs), "dsr_batch_download")
+            for (name, _), rec in zip(infos, recs):
+                ctx.check(getattr(ctx.lib, name)(slot.handle, rec), name)
+        finally:
+            slot.busy = False
+
+        def result(k, **more):
+            r = self._result(outs[k], self.code_len)
+            r.update(iters_done=int(outs[k].iters_done),
+                     fail_reason=L.FAIL_REASONS.get(int(outs[k].fail_reason), "?"), **more)
+            return r
+
+        return outs, recs, result
 
     def reconstruct_lidar_frame(self, velo, instance, masks, detections, camera, t_cam_velo, mesher=None, **params):
         """One KITTI keyframe straight from its Velodyne sweep, the 3-D detector's boxes and the
@@ -430,26 +444,11 @@ class Optimizer(object):
             return res
         dets, keep = U.lidar_dets(detections, self.code_len)
         ml = U.lidar_masks(masks)
-        outs = (L.ObjectOut * n)()
-        recs = (L.LidarDetOut * n)()
         ctx.check(ctx.lib.dsr_batch_refill_lidar(slot.handle, cam, p, L.fptr(tcv), L.fptr(velo), velo.shape[0],
                                                  velo.shape[1], L.iptr(instance), len(masks), ml, n, dets),
                   "dsr_batch_refill_lidar")
-        slot.busy = True
-        try:
-            ctx.check(ctx.lib.dsr_batch_run(slot.handle), "dsr_batch_run")
-            ctx.check(ctx.lib.dsr_batch_download(slot.handle, outs), "dsr_batch_download")
-            ctx.check(ctx.lib.dsr_batch_lidar_info(slot.handle, recs), "dsr_batch_lidar_info")
-        finally:
-            slot.busy = False
-        res = []
-        for k in range(n):
-            r = self._result(outs[k], self.code_len)
-            r["iters_done"] = int(outs[k].iters_done)
-            r["fail_reason"] = L.FAIL_REASONS.get(int(outs[k].fail_reason), "?")
-            r["ingest"] = U.lidar_record(recs[k])
-            res.append(r)
-        return self._mesh_results(res, mesher)
+        _, (recs,), result = self._run_slot(slot, n, [("dsr_batch_lidar_info", L.LidarDetOut)])
+        return self._mesh_results([result(k, ingest=U.lidar_record(recs[k])) for k in range(n)], mesher)
 
     MAX_SLOTS = 4
     # A slot batch is laid out for max_obj x max_rays x M ray samples whatever the fill, and every

@@ -195,6 +195,21 @@ def frame_images(depth, instance, camera):
     return depth, instance
 
 
+def _input_arrays(n, p):
+    """Zeroed ``(n, max_pts, 3)`` points, ``(n, max_pts + max_bg, 3)`` rays and ``(n, max_pts)`` depths
+    for the host ingest entry points to fill (at least one row, so that the pointers are real)."""
+    mp, mr = max(p.max_pts, 0), max(p.max_pts, 0) + max(p.max_bg, 0)
+    return [np.zeros((max(n, 1),) + tail, np.float32) for tail in ((mp, 3), (mr, 3), (mp,))]
+
+
+def _object(t_cam_obj, arrays, i, n_pts, n_rays, code):
+    """Detection ``i`` of the filled ``arrays`` as the tuple ``Optimizer.reconstruct_objects`` takes,
+    trimmed to its counts."""
+    pts, rays, dobs = arrays
+    return (np.array(t_cam_obj, np.float32).reshape(4, 4), pts[i, :n_pts].copy(), rays[i, :n_rays].copy(),
+            dobs[i, :n_pts].copy(), None if code is None else np.asarray(code, np.float32))
+
+
 def frame_inputs(depth, instance, detections, camera, **params):
     """What the reference builds per detection on the CPU — ``FrameWithLiDAR.get_detections`` +
     ``pixels_sampler`` (kitti_sequence.py:70-92, :139-146, :200-210), ``Frame.pixels_sampler``
@@ -213,23 +228,14 @@ def frame_inputs(depth, instance, detections, camera, **params):
     depth, instance = frame_images(depth, instance, cam)
     n = len(detections)
     dets, keep = frame_dets(detections)
-    mp, mr = max(p.max_pts, 0), max(p.max_pts, 0) + max(p.max_bg, 0)
-    pts = np.zeros((max(n, 1), mp, 3), np.float32)
-    rays = np.zeros((max(n, 1), mr, 3), np.float32)
-    dobs = np.zeros((max(n, 1), mp), np.float32)
+    arrays = _input_arrays(n, p)
     out = (L.FrameDetOut * max(n, 1))()
-    rc = lib.dsr_frame_inputs_host(cam, p, L.fptr(depth), L.iptr(instance), n, dets, L.fptr(pts), L.fptr(rays),
-                                   L.fptr(dobs), out)
+    rc = lib.dsr_frame_inputs_host(cam, p, L.fptr(depth), L.iptr(instance), n, dets, *map(L.fptr, arrays), out)
     if rc != 0:
         raise L.DsrError(f"dsr_frame_inputs_host failed ({rc}): bad camera, image or frame parameters")
-    objects, records = [], []
-    for i, det in enumerate(detections):
-        r = frame_record(out[i])
-        code = det.get("code")
-        objects.append((np.asarray(det["t_cam_obj"], np.float32).reshape(4, 4), pts[i, :r.n_pts].copy(),
-                        rays[i, :r.n_pts + r.n_bg].copy(), dobs[i, :r.n_pts].copy(),
-                        None if code is None else np.asarray(code, np.float32)))
-        records.append(r)
+    records = [frame_record(out[i]) for i in range(n)]
+    objects = [_object(det["t_cam_obj"], arrays, i, r.n_pts, r.n_pts + r.n_bg, det.get("code"))
+               for i, (det, r) in enumerate(zip(detections, records))]
     return objects, records
 
 
@@ -302,14 +308,11 @@ def frame_poses(depth, instance, detections, camera, pose_params=None, **params)
     n = len(detections)
     modes = frame_pose_modes(detections)
     dets, keep = frame_dets([_with_pose(d) for d in detections])
-    mp, mr = max(p.max_pts, 0), max(p.max_pts, 0) + max(p.max_bg, 0)
-    pts = np.zeros((max(n, 1), mp, 3), np.float32)
-    rays = np.zeros((max(n, 1), mr, 3), np.float32)
-    dobs = np.zeros((max(n, 1), mp), np.float32)
+    arrays = _input_arrays(n, p)
     out = (L.FrameDetOut * max(n, 1))()
     pout = (L.FramePoseOut * max(n, 1))()
-    rc = lib.dsr_frame_poses_host(cam, p, q, L.fptr(depth), L.iptr(instance), n, dets, L.iptr(modes), L.fptr(pts),
-                                  L.fptr(rays), L.fptr(dobs), out, pout)
+    rc = lib.dsr_frame_poses_host(cam, p, q, L.fptr(depth), L.iptr(instance), n, dets, L.iptr(modes),
+                                  *map(L.fptr, arrays), out, pout)
     if rc != 0:
         raise L.DsrError(f"dsr_frame_poses_host failed ({rc}): bad camera, image, frame or pose parameters")
     objects, records, poses = [], [], []
@@ -321,9 +324,7 @@ def frame_poses(depth, instance, detections, camera, pose_params=None, **params)
             n_p, n_r = pr.n_kept, pr.n_kept + r.n_bg
         else:
             n_p = n_r = 0
-        code = det.get("code")
-        objects.append((pr.t_cam_obj.copy(), pts[i, :n_p].copy(), rays[i, :n_r].copy(), dobs[i, :n_p].copy(),
-                        None if code is None else np.asarray(code, np.float32)))
+        objects.append(_object(pr.t_cam_obj, arrays, i, n_p, n_r, det.get("code")))
         records.append(r)
         poses.append(pr)
     return objects, records, poses
@@ -438,24 +439,18 @@ def lidar_inputs(velo, instance, masks, detections, camera, t_cam_velo, **params
     n = len(detections)
     dets, keep = lidar_dets(detections)
     ml = lidar_masks(masks)
-    mp, mr = max(p.max_pts, 0), max(p.max_pts, 0) + max(p.max_bg, 0)
-    pts = np.zeros((max(n, 1), mp, 3), np.float32)
-    rays = np.zeros((max(n, 1), mr, 3), np.float32)
-    dobs = np.zeros((max(n, 1), mp), np.float32)
+    arrays = _input_arrays(n, p)
     out = (L.LidarDetOut * max(n, 1))()
     rc = lib.dsr_lidar_inputs_host(cam, p, L.fptr(tcv), L.fptr(velo), velo.shape[0], velo.shape[1], L.iptr(instance),
-                                   len(masks), ml, n, dets, L.fptr(pts), L.fptr(rays), L.fptr(dobs), out)
+                                   len(masks), ml, n, dets, *map(L.fptr, arrays), out)
     if rc != 0:
         raise L.DsrError(f"dsr_lidar_inputs_host failed ({rc}): bad camera, sweep, masks, detections or lidar "
                          "parameters")
     objects, records = [], []
     for i, det in enumerate(detections):
         r = lidar_record(out[i])
-        ok = r.status == L.LIDAR_OK
-        n_p, n_r = (r.n_pts, r.n_pts + r.n_bg) if ok else (0, 0)
-        code = det.get("code") if isinstance(det, dict) else None
-        objects.append((np.asarray(r.t_cam_obj, np.float32).reshape(4, 4), pts[i, :n_p].copy(), rays[i, :n_r].copy(), dobs[i, :n_p].copy(),
-                        None if code is None else np.asarray(code, np.float32)))
+        n_p, n_r = (r.n_pts, r.n_pts + r.n_bg) if r.status == L.LIDAR_OK else (0, 0)
+        objects.append(_object(r.t_cam_obj, arrays, i, n_p, n_r, det.get("code") if isinstance(det, dict) else None))
         records.append(r)
     return objects, records
 

@@ -87,10 +87,10 @@ def _pose_of(det):
 
 
 @pytest.fixture(scope="module")
-def sweeps(gpu_decoder):
+def rendered(gpu_decoder):
     """Two rendered keyframes of two objects, each back-projected into a velodyne sweep: the second
     at other poses and with label 1 erased from the image.  The detections handed to the ingest sit
-    5 cm beside the rendered poses."""
+    5 cm beside the rendered poses.  Per keyframe (sweep, instance image, detections, depth image)."""
     from reconstruct.optimizer import SdfRenderer
 
     ren = SdfRenderer(gpu_decoder, RW, RH, RCAM["fx"], RCAM["fy"], RCAM["cx"], RCAM["cy"])
@@ -108,9 +108,15 @@ def sweeps(gpu_decoder):
         assert 1000 < velo.shape[0] < 7000
         if k == 1:
             inst[inst == 1] = -1
-        out.append((velo, inst, [_det(i, shift + 0.05) for i in range(2)]))
+        out.append((velo, inst, [_det(i, shift + 0.05) for i in range(2)], depth))
     ren.close()
     return out
+
+
+@pytest.fixture(scope="module")
+def sweeps(rendered):
+    """The keyframes of ``rendered`` as (sweep, instance image, detections)."""
+    return [r[:3] for r in rendered]
 
 
 class Batch:
@@ -287,6 +293,87 @@ def test_capacity_errors(gpu_decoder, sweeps):
             lib.dsr_batch_destroy(h)
     finally:
         b.close()
+
+
+def test_one_batch_takes_every_kind_of_fill(gpu_decoder, rendered):
+    """One batch refilled from a frame, a sweep, a frame with poses, host arrays and a frame again:
+    after each fill its downloaded out-records and its info records are those of a fresh batch given
+    only that fill, and the info calls of the other kinds refuse.  The ingest block of two
+    detections in a frame at 96 x 72 takes 2 x 27648 B of images and under 6 KB of tables and
+    records (dsr_frame.hpp: frame_dev_bytes + frame_pose_dev_bytes), that of the sweep 16 B per
+    point + 27648 B of image + 5120 B of masks + 7 KB of tables (dsr_lidar.hpp: lidar_dev_bytes), so
+    above 1400 points the sweep's block is the larger: the second fill grows the block, and the
+    third and fifth are laid out in a block left larger than they need."""
+    from reconstruct import _libdsr as L
+    from reconstruct import utils as U
+
+    (velo, inst, ldets, depth), (_, inst1, _, depth1) = rendered
+    assert velo.shape[0] > 1400
+    opt = _opt(gpu_decoder)
+    ctx, lib = opt._ctx, opt._ctx.lib
+    cam = U.frame_camera(RCAM)
+    given = [dict(label=i, t_cam_obj=_pose_of(ldets[i]), code=_code(i)) for i in range(2)]
+    keep = []
+
+    def frame(b, depth, inst):
+        fd, k = U.frame_dets(given)
+        keep.append(k)
+        ctx.check(lib.dsr_batch_refill_frame(b.h, cam, U.frame_params(**PARAMS), L.fptr(depth), L.iptr(inst), 2, fd),
+                  "refill_frame")
+        return b.run(2)
+
+    def sweep(b):
+        v, i, tcv = U.lidar_sweep(velo, inst, cam, LC.TCV)
+        ld, k = U.lidar_dets(ldets)
+        keep.append(k)
+        ctx.check(lib.dsr_batch_refill_lidar(b.h, cam, U.lidar_params(**PARAMS), L.fptr(tcv), L.fptr(v), v.shape[0],
+                                             v.shape[1], L.iptr(i), len(MASKS), U.lidar_masks(MASKS), 2, ld),
+                  "refill_lidar")
+        return b.run(2)
+
+    def poses(b):
+        dets = [given[0], dict(given[1], t_cam_obj=None)]         # one pose given, one from the cuboid
+        fd, k = U.frame_dets([U._with_pose(d) for d in dets])
+        keep.append(k)
+        modes = U.frame_pose_modes(dets)
+        ctx.check(lib.dsr_batch_refill_frame_poses(b.h, cam, U.frame_params(**PARAMS), U.frame_pose_params(),
+                                                   L.fptr(depth), L.iptr(inst), 2, fd, L.iptr(modes)),
+                  "refill_frame_poses")
+        return b.run(2)
+
+    def info(b):
+        """Per kind the records its info call returns, or None where the call refuses."""
+        fr, pr, lr = (L.FrameDetOut * 2)(), (L.FramePoseOut * 2)(), (L.LidarDetOut * 2)()
+        f = [U.frame_record(r) for r in fr] if lib.dsr_batch_frame_info(b.h, fr) == 0 else None
+        p = ([(r.status, r.n_in, r.n_near, r.n_kept, bytes(r.dims), bytes(r.eig), bytes(r.t_cam_obj)) for r in pr]
+             if lib.dsr_batch_frame_pose_info(b.h, pr) == 0 else None)
+        s = [U.lidar_record(r) for r in lr] if lib.dsr_batch_lidar_info(b.h, lr) == 0 else None
+        return f, p, s
+
+    fills = [("frame", lambda b: frame(b, depth, inst)),
+             ("sweep", sweep),
+             ("poses", poses),
+             ("objects", lambda b: b.host(velo, inst, ldets, **PARAMS)[0]),
+             ("frame", lambda b: frame(b, depth1, inst1))]
+    answers = dict(frame=(True, False, False), sweep=(False, False, True), poses=(True, True, False),
+                   objects=(False, False, False))
+    one = Batch(opt, 2, 256, 456)
+    try:
+        seen = []
+        for kind, fill in fills:
+            got = (_bytes(fill(one)), info(one))
+            fresh = Batch(opt, 2, 256, 456)
+            try:
+                want = (_bytes(fill(fresh)), info(fresh))
+            finally:
+                fresh.close()
+            assert got == want, kind
+            assert tuple(r is not None for r in got[1]) == answers[kind], kind
+            seen.append(got)
+        assert seen[0][1][0][1].status == 0 and seen[4][1][0][1].status != 0     # label 1: there, then erased
+        assert seen[0][0] != seen[4][0]                                          # the two frame fills differ
+    finally:
+        one.close()
 
 
 def _same(a, b):
