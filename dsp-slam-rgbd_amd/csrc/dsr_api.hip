@@ -28,6 +28,7 @@
 #include "dsr_scene.hpp"
 #include "dsr_frame.hpp"
 #include "dsr_lidar.hpp"
+#include "dsr_track.hpp"
 
 #ifndef DSR_DEFAULT_FWD_VARIANT
 #define DSR_DEFAULT_FWD_VARIANT 12  // split-fp16 (3xFP16) + s_setprio (A/B: tools/fwd_variants.py)
@@ -1802,13 +1803,12 @@ struct IngestCall {
 };
 }  // namespace
 
-// Waits until the previous refill's copies have left the staging buffers and the pinned block,
-// then makes the ingest block hold `up` uploaded bytes of `all` (0, 0: a fill without one).  Both
-// halves only grow; the device block is replaced only once no kernel can still read it.
-static int refill_begin(dsr_batch* b, size_t up, size_t all) {
-  dsr_ctx* ctx = b->ctx;
-  dsr_batch::IngestBlock& g = b->ingest;
-  DSR_CHECK(ctx, hipEventSynchronize(b->up_ev));
+// Waits until the copies recorded in up_ev have left the owner's staging buffers and the pinned
+// half of its ingest block g, then makes the block hold `up` uploaded bytes of `all` (0, 0: a fill
+// without one).  Both halves only grow; the device block is replaced only once no kernel can still
+// read it.  The owner is a batch (refill_begin) or a tracker (dsr_tracker_track_lidar).
+static int ingest_fit(dsr_ctx* ctx, dsr_batch::IngestBlock& g, hipEvent_t up_ev, size_t up, size_t all) {
+  DSR_CHECK(ctx, hipEventSynchronize(up_ev));
   if (up > g.host_bytes) {
     if (g.host) hipHostFree(g.host);
     g.host = nullptr;
@@ -1826,6 +1826,10 @@ static int refill_begin(dsr_batch* b, size_t up, size_t all) {
     g.dev_bytes = all;
   }
   return 0;
+}
+
+static int refill_begin(dsr_batch* b, size_t up, size_t all) {
+  return ingest_fit(b->ctx, b->ingest, b->up_ev, up, all);
 }
 
 // Stages every slot (fill[0 .. n) and the empty rest), then uploads the first `stages` staging
@@ -4362,6 +4366,305 @@ int dsr_pose_only(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* 
   x.n_pts = n_pts;
   x.code = code;
   return dsr_pose_only_batch(ctx, dec, p, 1, &x, t_out);
+}
+
+
+// ------------------------------------------------------------------------------------
+// tracker: dsr_pose_only_batch as a resident handle (dsr_tracker_*; the
+// kernels and the host rule of the start pose in dsr_track.hpp)
+// ------------------------------------------------------------------------------------
+struct dsr_tracker {
+  dsr_ctx* ctx = nullptr;
+  const dsr_decoder* dec = nullptr;
+  GNParams P{};
+  int iters = 0, max_obj = 0, max_pts = 0, tpo = 0;
+  float* lnw = nullptr;              // LayerNorm decoders: the context stream's Jacobian workspace
+  DevArena mem;
+  // device; head = t_in | z | cnt and tail = out | recs are one block each (one copy each way)
+  char *head = nullptr, *tail = nullptr;
+  float *t_in = nullptr, *z = nullptr, *zb = nullptr, *b0 = nullptr, *b4 = nullptr;
+  int *cnt = nullptr, *is_oc = nullptr, *n_tiles = nullptr;
+  float *pts = nullptr, *res = nullptr, *slots = nullptr, *out = nullptr;
+  ObjDesc* desc = nullptr;
+  ObjState* st = nullptr;
+  Tile* tiles = nullptr;
+  dsr_track_out* recs = nullptr;
+  // pinned: head | pts | tail
+  char* host = nullptr;
+  size_t head_bytes = 0, pts_bytes = 0, tail_bytes = 0;
+  dsr_batch::IngestBlock sweep;      // a sweep call's block (lidar_carve without an image): it grows
+  hipEvent_t up_ev = nullptr;        // recorded after a call's uploads
+  hipEvent_t done_ev = nullptr;      // recorded after a call's copy into the pinned tail
+  int n_last = 0;                    // objects of the last call (0: none yet)
+  std::vector<float> scale;          // their scales (optimizer.py:85 on the host)
+};
+
+// the parts of head and tail, on either side
+static size_t track_head_z(int max_obj) { return frame_up256(sizeof(float) * 16 * (size_t)max_obj); }
+static size_t track_head_cnt(int max_obj) { return track_head_z(max_obj) + frame_up256(sizeof(float) * CODE * (size_t)max_obj); }
+static size_t track_tail_recs(int max_obj) { return frame_up256(sizeof(float) * 16 * (size_t)max_obj); }
+
+int dsr_tracker_destroy(dsr_tracker* tr) {
+  if (!tr) return 0;
+  std::lock_guard<std::recursive_mutex> run(tr->ctx->run_mu);
+  hipSetDevice(tr->ctx->device);
+  hipStreamSynchronize(tr->ctx->stream);
+  if (tr->up_ev) hipEventDestroy(tr->up_ev);
+  if (tr->done_ev) hipEventDestroy(tr->done_ev);
+  if (tr->host) hipHostFree(tr->host);
+  if (tr->sweep.host) hipHostFree(tr->sweep.host);
+  if (tr->sweep.dev) hipFree(tr->sweep.dev);
+  delete tr;
+  return 0;
+}
+
+int dsr_tracker_create(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p, int max_obj, int max_pts,
+                       dsr_tracker** out) {
+  if (!ctx || !dec || !p || !out) return fail(ctx, "null argument");
+  *out = nullptr;
+  if (max_obj < 1) return fail(ctx, "tracker: max_obj must be >= 1");
+  if (max_pts < 1 || max_pts > TRACK_MAX_PTS) return fail(ctx, "tracker: max_pts must be in [1, 2^20]");
+  if ((long long)max_obj * max_pts > TRACK_MAX_ROWS) return fail(ctx, "tracker: max_obj x max_pts must be at most 2^22");
+  if (p->code_len != dec->code_len) return fail(ctx, "optimizer code_len != decoder code_len");
+  float* lnw = nullptr;
+  if (int rc = decoder_ready(ctx, dec, true, &lnw)) return rc;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  auto* tr = new dsr_tracker();
+  tr->ctx = ctx;
+  tr->dec = dec;
+  tr->P = make_params(p, false);
+  tr->P.raw_residual = 1;
+  tr->iters = p->pose_only_iterations;
+  tr->max_obj = max_obj;
+  tr->max_pts = max_pts;
+  tr->tpo = track_tiles_per_obj(max_pts);
+  tr->lnw = lnw;
+  const size_t no = (size_t)max_obj, rows = no * max_pts, nt = no * tr->tpo;
+  tr->head_bytes = track_head_cnt(max_obj) + frame_up256(sizeof(int) * no);
+  tr->pts_bytes = frame_up256(sizeof(float) * 3 * rows);
+  tr->tail_bytes = track_tail_recs(max_obj) + frame_up256(sizeof(dsr_track_out) * no);
+  DevArena& M = tr->mem;
+  bool ok = M.alloc(&tr->head, tr->head_bytes) && M.alloc(&tr->tail, tr->tail_bytes) && M.alloc(&tr->pts, 3 * rows) &&
+            M.alloc(&tr->res, rows) && M.alloc(&tr->desc, no) && M.alloc(&tr->st, no) && M.alloc(&tr->zb, CODE * no) &&
+            M.alloc(&tr->b0, HID * no) && M.alloc(&tr->b4, HID * no) && M.alloc(&tr->is_oc, no) &&
+            M.alloc(&tr->tiles, nt) && M.alloc(&tr->n_tiles, 1) && M.alloc(&tr->slots, SLOT_FLOATS * nt);
+  ok = ok && hipHostMalloc((void**)&tr->host, tr->head_bytes + tr->pts_bytes + tr->tail_bytes, hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&tr->up_ev, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&tr->done_ev, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipMemset(tr->is_oc, 0, sizeof(int) * no) == hipSuccess;      // t_in is camera<-object (:57)
+  if (!ok) {
+    (void)hipGetLastError();
+    dsr_tracker_destroy(tr);
+    return fail(ctx, "hipMalloc failed (tracker)");
+  }
+  std::memset(tr->host, 0, tr->head_bytes + tr->pts_bytes + tr->tail_bytes);
+  tr->t_in = reinterpret_cast<float*>(tr->head);
+  tr->z = reinterpret_cast<float*>(tr->head + track_head_z(max_obj));
+  tr->cnt = reinterpret_cast<int*>(tr->head + track_head_cnt(max_obj));
+  tr->out = reinterpret_cast<float*>(tr->tail);
+  tr->recs = reinterpret_cast<dsr_track_out*>(tr->tail + track_tail_recs(max_obj));
+  tr->scale.assign(no, 1.f);
+  *out = tr;
+  return 0;
+}
+
+static bool track_pose_ok(const float* t, float scale) {
+  if (!(scale > 0.f) || std::isinf(scale)) return false;
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(t[i])) return false;
+  return true;
+}
+
+// object o's staged head rows: t_in = t_co_se3 with the fp32 scale on its rotation block
+// (optimizer.py:56), the code padded with zeros, the count (0 for a sweep call: k_lidar_scan's)
+static void track_stage(dsr_tracker* tr, int o, const float* t_co_se3, float scale, const float* code, int n_pts) {
+  float* t = reinterpret_cast<float*>(tr->host) + (size_t)16 * o;
+  for (int i = 0; i < 16; ++i) t[i] = t_co_se3[i];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) t[i * 4 + j] = t[i * 4 + j] * scale;
+  float* z = reinterpret_cast<float*>(tr->host + track_head_z(tr->max_obj)) + (size_t)CODE * o;
+  std::memset(z, 0, sizeof(float) * CODE);
+  std::memcpy(z, code, sizeof(float) * tr->dec->code_len);
+  reinterpret_cast<int*>(tr->host + track_head_cnt(tr->max_obj))[o] = n_pts;
+  tr->scale[o] = scale;
+}
+
+// Everything of a call after its staging, on the context stream: the uploads (the head, then
+// pts_floats of host rows or sweep_up bytes of the sweep block S lays out), the fill's kernels, the
+// GN loop of dsr_pose_only_batch with the filter and the tile table on the device, and the copy
+// into the pinned tail.  tile_bound: the call's tiles at most (sizes the Jacobian grid).
+static int track_run(dsr_tracker* tr, int n, size_t pts_floats, int tile_bound, const dsr_lidar_params* LP,
+                     const LidarShape* S, const float* tcv, size_t sweep_up) {
+  dsr_ctx* ctx = tr->ctx;
+  hipStream_t s = ctx->stream;
+  DSR_CHECK(ctx, hipMemcpyAsync(tr->head, tr->host, tr->head_bytes, hipMemcpyHostToDevice, s));
+  if (pts_floats)
+    DSR_CHECK(ctx, hipMemcpyAsync(tr->pts, tr->host + tr->head_bytes, sizeof(float) * pts_floats, hipMemcpyHostToDevice, s));
+  LidarDev L{};
+  if (S) {
+    DSR_CHECK(ctx, hipMemcpyAsync(tr->sweep.dev, tr->sweep.host, sweep_up, hipMemcpyHostToDevice, s));
+    L = lidar_carve(tr->sweep.dev, *S);
+  }
+  DSR_CHECK(ctx, hipEventRecord(tr->up_ev, s));
+  const int nc = S ? lidar_chunks(S->n_velo) : 0;
+  const unsigned gc = (unsigned)((nc + FRAME_WAVES - 1) / FRAME_WAVES);
+  if (S) {                                  // the crop passes of lidar_launch; no image pass runs
+    if (nc > 0)
+      hipLaunchKernelGGL(k_lidar_count, dim3(gc, n), dim3(FRAME_WG), 0, s, (const float*)L.velo, S->n_velo, S->stride,
+                         (const LidarDet*)L.dets, nc, L.cnt);
+    hipLaunchKernelGGL(k_lidar_scan, dim3(n), dim3(FRAME_WG), 0, s, *LP, (const LidarDet*)L.dets, nc, (const int*)L.cnt,
+                       L.coff, L.hits, L.nproj, L.recs);
+  }
+  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(TILE_SCAN_THREADS), 0, s, n, tr->max_pts, tr->tpo, (const int*)tr->cnt,
+                     (const dsr_lidar_det_out*)(S ? L.recs : nullptr), tr->desc, tr->recs, tr->tiles, tr->n_tiles);
+  if (S && nc > 0)
+    hipLaunchKernelGGL(k_lidar_emit<false>, dim3(gc, n), dim3(FRAME_WG), 0, s, FrameCam{}, *LP, lidar_xf(tcv),
+                       (const float*)L.velo, S->n_velo, S->stride, (const int*)nullptr, (const dsr_lidar_mask*)nullptr, 0,
+                       (const LidarDet*)L.dets, nc, (const int*)L.cnt, (const int*)L.coff,
+                       (const dsr_lidar_det_out*)L.recs, (int*)nullptr, (int*)nullptr, (const ObjDesc*)tr->desc, tr->pts,
+                       (float*)nullptr, (float*)nullptr);
+  const DevDecoder& D = tr->dec->D;
+  fold_codes(s, D, tr->z, n, tr->b0, tr->b4);
+  hipLaunchKernelGGL(k_init_state, dim3(n), dim3(64), 0, s, n, (const float*)tr->t_in, (const int*)tr->is_oc,
+                     (const float*)tr->z, tr->st, tr->zb, 1);                          // :57 t_obj_cam = inv
+  JacQuery jq{tr->tiles, tr->n_tiles, tr->desc, tr->b0, tr->b4};
+  jq.st = tr->st;
+  jq.surf_pts = tr->pts;
+  jq.P = tr->P;
+  jq.slots = tr->slots;
+  jq.lnw = tr->lnw;
+  const int grid = std::max(1, std::min(ctx->n_cu, tile_bound));
+  for (int e = 0; e < tr->iters; ++e) {
+    const bool filter = (e == 4) && (e + 1 < tr->iters);   // :77-79 inlier filter (effective only past 5 iters)
+    jq.res_out = filter ? tr->res : nullptr;
+    if (tile_bound > 0) launch_jac(s, grid, D, jq);
+    hipLaunchKernelGGL(k_solve_pose, dim3(n), dim3(256), 0, s, (const ObjDesc*)tr->desc, tr->st, (const float*)tr->slots);
+    if (filter && tile_bound > 0) {
+      hipLaunchKernelGGL(k_track_filter, dim3(n), dim3(FRAME_WG), 0, s, tr->desc, (const float*)tr->res, tr->pts, tr->recs);
+      hipLaunchKernelGGL(k_track_tiles, dim3(1), dim3(TILE_SCAN_THREADS), 0, s, n, (const ObjDesc*)tr->desc, tr->tiles,
+                         tr->n_tiles);
+    }
+  }
+  hipLaunchKernelGGL(k_inv_out, dim3((n + 63) / 64), dim3(64), 0, s, n, (const ObjState*)tr->st, tr->out);   // :84
+  DSR_CHECK(ctx, hipGetLastError());
+  DSR_CHECK(ctx, hipMemcpyAsync(tr->host + tr->head_bytes + tr->pts_bytes, tr->tail, tr->tail_bytes,
+                                hipMemcpyDeviceToHost, s));
+  DSR_CHECK(ctx, hipEventRecord(tr->done_ev, s));
+  tr->n_last = n;
+  return 0;
+}
+
+int dsr_tracker_track(dsr_tracker* tr, int n_obj, const dsr_pose_in* in) {
+  if (!tr) return -2;
+  dsr_ctx* ctx = tr->ctx;
+  if (!in) return fail(ctx, "null argument");
+  if (n_obj < 1 || n_obj > tr->max_obj) return fail(ctx, "tracker: n_obj must be in [1, the tracker's max_obj]");
+  long long tiles = 0;
+  for (int o = 0; o < n_obj; ++o) {
+    if (!in[o].code || (in[o].n_pts > 0 && !in[o].pts)) return fail(ctx, "null argument");
+    if (in[o].n_pts < 0 || in[o].n_pts > tr->max_pts) return fail(ctx, "tracker: an object's points exceed the tracker's max_pts");
+    if (!track_pose_ok(in[o].t_co_se3, in[o].scale)) return fail(ctx, "tracker: scale must be positive and finite, the pose finite");
+    tiles += (in[o].n_pts + TILE - 1) / TILE;
+  }
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  DSR_CHECK(ctx, hipEventSynchronize(tr->up_ev));    // the previous call's uploads have left the pinned block
+  float* hp = reinterpret_cast<float*>(tr->host + tr->head_bytes);
+  for (int o = 0; o < n_obj; ++o) {
+    const dsr_pose_in& x = in[o];
+    track_stage(tr, o, x.t_co_se3, x.scale, x.code, x.n_pts);
+    if (x.n_pts) std::memcpy(hp + (size_t)o * tr->max_pts * 3, x.pts, sizeof(float) * 3 * x.n_pts);
+  }
+  // objects 0 .. n_obj - 1 at the fixed stride: up to the last object's last row
+  const size_t up = ((size_t)(n_obj - 1) * tr->max_pts + in[n_obj - 1].n_pts) * 3;
+  return track_run(tr, n_obj, tiles ? up : 0, (int)tiles, nullptr, nullptr, nullptr, 0);
+}
+
+// dsr_lidar_inputs_host's argument errors for what a tracker call reads: the fields that are not
+// read are given valid values (a 1 x 1 camera and image, no masks, no background grid)
+static const char* track_lidar_error(const dsr_lidar_params* P, bool crop, const float* tcv, const float* velo,
+                                     int n_velo, int stride, int n_det, const dsr_lidar_det* dets) {
+  if (!P) return "lidar: null camera or parameters";
+  const dsr_camera cam{1, 1, 1.f, 1.f, 0.f, 0.f};
+  const int inst = 0;
+  const dsr_lidar_params Q{crop ? P->max_pts : 1, 0, 1, 0, 0, crop ? P->radius : 1.f, P->box_margin};
+  return lidar_args_error(&cam, &Q, lidar_rigid(tcv), velo, n_velo, stride, &inst, 0, nullptr, n_det, dets);
+}
+
+int dsr_lidar_track_prep_host(const dsr_lidar_params* params, const float* t_cam_velo, int n_det,
+                              const dsr_lidar_det* dets, float* t_co_se3, float* det_scale) {
+  if (track_lidar_error(params, false, t_cam_velo, nullptr, 0, 3, n_det, dets)) return -2;
+  if (n_det > 0 && (!t_co_se3 || !det_scale)) return -2;
+  for (int d = 0; d < n_det; ++d) lidar_track_prep(*params, t_cam_velo, dets[d], t_co_se3 + (size_t)16 * d, det_scale + d);
+  return 0;
+}
+
+int dsr_tracker_track_lidar(dsr_tracker* tr, const dsr_lidar_params* params, const float* t_cam_velo,
+                            const float* velo, int n_velo, int stride, int n_det, const dsr_lidar_det* dets,
+                            const dsr_track_det* prior) {
+  if (!tr) return -2;
+  dsr_ctx* ctx = tr->ctx;
+  if (!params || !t_cam_velo || !dets || !prior) return fail(ctx, "null argument");
+  if (n_det < 1 || n_det > tr->max_obj) return fail(ctx, "tracker: n_det must be in [1, the tracker's max_obj]");
+  if (const char* m = track_lidar_error(params, true, t_cam_velo, velo, n_velo, stride, n_det, dets)) return fail(ctx, m);
+  if (params->max_pts > tr->max_pts) return fail(ctx, "tracker: max_pts exceeds the tracker's max_pts");
+  for (int o = 0; o < n_det; ++o) {
+    if (!dets[o].code) return fail(ctx, "null argument");
+    const float eye[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+    if (!track_pose_ok(prior[o].pose_given ? prior[o].t_co_se3 : eye, prior[o].scale))
+      return fail(ctx, "tracker: scale must be positive and finite, a given pose finite");
+  }
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  // the sweep block is the ingest's without an image: sweep | masks (unused) | prepared detections
+  // up, then the crop tables and records
+  const LidarShape S{n_velo, stride, 0, 0, n_det};
+  const size_t up = lidar_upload_bytes(S);
+  if (int rc = ingest_fit(ctx, tr->sweep, tr->up_ev, up, lidar_dev_bytes(S))) return rc;
+  const int no_image = 0;
+  lidar_pack(tr->sweep.host, S, *params, t_cam_velo, velo, &no_image, 0, nullptr, dets);
+  for (int o = 0; o < n_det; ++o) {
+    float t[16], det_scale;
+    lidar_track_prep(*params, t_cam_velo, dets[o], t, &det_scale);
+    track_stage(tr, o, prior[o].pose_given ? prior[o].t_co_se3 : t, prior[o].scale, dets[o].code, 0);
+  }
+  const int tiles = n_det * track_tiles_per_obj(params->max_pts);
+  return track_run(tr, n_det, 0, tiles, params, &S, t_cam_velo, up);
+}
+
+int dsr_tracker_query(dsr_tracker* tr) {
+  if (!tr) return -2;
+  if (!tr->n_last) return fail(tr->ctx, "tracker has not run");
+  std::lock_guard<std::recursive_mutex> run(tr->ctx->run_mu);
+  hipSetDevice(tr->ctx->device);
+  const hipError_t e = hipEventQuery(tr->done_ev);
+  if (e == hipSuccess) return 1;
+  if (e == hipErrorNotReady) return 0;
+  return fail(tr->ctx, std::string("hipEventQuery: ") + hipGetErrorString(e));
+}
+
+int dsr_tracker_download(dsr_tracker* tr, float* t_out, dsr_track_out* rec) {
+  if (!tr) return -2;
+  dsr_ctx* ctx = tr->ctx;
+  if (!t_out) return fail(ctx, "null argument");
+  if (!tr->n_last) return fail(ctx, "tracker has not run");
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  DSR_CHECK(ctx, hipEventSynchronize(tr->done_ev));
+  const char* tail = tr->host + tr->head_bytes + tr->pts_bytes;
+  const float* T = reinterpret_cast<const float*>(tail);
+  const dsr_track_out* R = reinterpret_cast<const dsr_track_out*>(tail + track_tail_recs(tr->max_obj));
+  for (int o = 0; o < tr->n_last; ++o) {
+    float* to = t_out + 16 * o;
+    for (int i = 0; i < 16; ++i) to[i] = T[16 * o + i];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) to[i * 4 + j] = to[i * 4 + j] / tr->scale[o];          // :85
+    if (R[o].status != DSR_TRACK_OK)    // J^T J / 0 in the reference: the pose turns NaN
+      for (int i = 0; i < 16; ++i) to[i] = __builtin_nanf("");
+    if (rec) rec[o] = R[o];
+  }
+  return 0;
 }
 
 }  // extern "C"

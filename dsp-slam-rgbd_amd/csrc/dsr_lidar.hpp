@@ -313,6 +313,9 @@ __global__ __launch_bounds__(FRAME_WG) void k_lidar_scan(dsr_lidar_params P, con
 // in-points) and writes its surface point, foreground ray and depth; a projected row counts for the
 // first mask-list entry carrying its pixel's label (integer atomics).  grid as pass 1.  Outputs go
 // to the slots of desc (a capacity batch) or, desc == null, to fixed strides per detection.
+// IMG = false (the tracker, dsr_track.hpp): the surface points alone — no ray, no depth, no
+// projection; C, inst, masks, hits, nproj, rays and dobs are not read.
+template <bool IMG>
 __global__ __launch_bounds__(FRAME_WG) DSR_NO_PK_F32 void k_lidar_emit(FrameCam C, dsr_lidar_params P, LidarXf X,
                                                          const float* __restrict__ velo, int n_velo, int stride,
                                                          const int* __restrict__ inst,
@@ -323,27 +326,34 @@ __global__ __launch_bounds__(FRAME_WG) DSR_NO_PK_F32 void k_lidar_emit(FrameCam 
                                                          int* __restrict__ hits, int* __restrict__ nproj,
                                                          const ObjDesc* __restrict__ desc, float* __restrict__ pts,
                                                          float* __restrict__ rays, float* __restrict__ dobs) {
-  __shared__ int mlabel[DSR_LIDAR_MAX_MASKS];
+  __shared__ int mlabel[IMG ? DSR_LIDAR_MAX_MASKS : 1];
   const int lane = threadIdx.x & 63, c = blockIdx.x * FRAME_WAVES + (threadIdx.x >> 6), d = blockIdx.y;
-  if ((int)threadIdx.x < n_masks) mlabel[threadIdx.x] = masks[threadIdx.x].label;
-  __syncthreads();
+  if constexpr (IMG) {
+    if ((int)threadIdx.x < n_masks) mlabel[threadIdx.x] = masks[threadIdx.x].label;
+    __syncthreads();
+  }
   if (c >= n_chunks) return;
   if ((cnt[(size_t)d * n_chunks + c] >> 8) == 0) return;
   const long long N = recs[d].n_crop, n = recs[d].n_pts;
   const long long base = coff[(size_t)d * n_chunks + c];
-  float *op, *orr, *oz;
+  float *op, *orr = nullptr, *oz = nullptr;
   if (desc) {
     op = pts + (size_t)desc[d].pts_off * 3;
-    orr = rays + (size_t)desc[d].ray_off * 3;
-    oz = dobs + desc[d].ray_off;
+    if constexpr (IMG) {
+      orr = rays + (size_t)desc[d].ray_off * 3;
+      oz = dobs + desc[d].ray_off;
+    }
   } else {
     op = pts + (size_t)d * P.max_pts * 3;
-    orr = rays + (size_t)d * ((size_t)P.max_pts + P.max_bg) * 3;
-    oz = dobs + (size_t)d * P.max_pts;
+    if constexpr (IMG) {
+      orr = rays + (size_t)d * ((size_t)P.max_pts + P.max_bg) * 3;
+      oz = dobs + (size_t)d * P.max_pts;
+    }
   }
   const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
   const int i = c * 64 + lane;
-  bool in = false, proj = false;
+  bool in = false;
+  [[maybe_unused]] bool proj = false;
   float px = 0.f, py = 0.f, pz = 0.f;
   if (i < n_velo) {
     const float* p = velo + (size_t)i * stride;
@@ -356,24 +366,28 @@ __global__ __launch_bounds__(FRAME_WG) DSR_NO_PK_F32 void k_lidar_emit(FrameCam 
     if (row >= 0 && row < n) {
       float q[3];
       lidar_q(X, px, py, pz, q);
-      const float rx = q[0] / q[2], ry = q[1] / q[2];
       op[row * 3] = q[0]; op[row * 3 + 1] = q[1]; op[row * 3 + 2] = q[2];
-      orr[row * 3] = rx; orr[row * 3 + 1] = ry; orr[row * 3 + 2] = 1.f;
-      oz[row] = q[2];
-      int u, v;
-      if (lidar_project(C, q[2], rx, ry, &u, &v)) {
-        proj = true;
-        const int label = inst[(size_t)v * C.W + u];
-        for (int j = 0; j < n_masks; ++j)
-          if (mlabel[j] == label) {
-            atomicAdd(&hits[(size_t)d * DSR_LIDAR_MAX_MASKS + j], 1);
-            break;
-          }
+      if constexpr (IMG) {
+        const float rx = q[0] / q[2], ry = q[1] / q[2];
+        orr[row * 3] = rx; orr[row * 3 + 1] = ry; orr[row * 3 + 2] = 1.f;
+        oz[row] = q[2];
+        int u, v;
+        if (lidar_project(C, q[2], rx, ry, &u, &v)) {
+          proj = true;
+          const int label = inst[(size_t)v * C.W + u];
+          for (int j = 0; j < n_masks; ++j)
+            if (mlabel[j] == label) {
+              atomicAdd(&hits[(size_t)d * DSR_LIDAR_MAX_MASKS + j], 1);
+              break;
+            }
+        }
       }
     }
   }
-  const unsigned long long pb = __ballot(proj);
-  if (lane == 0 && pb) atomicAdd(&nproj[d], __popcll(pb));
+  if constexpr (IMG) {
+    const unsigned long long pb = __ballot(proj);
+    if (lane == 0 && pb) atomicAdd(&nproj[d], __popcll(pb));
+  }
 }
 
 // Pass 4: one workgroup per detection — the first entry with the most hits, the threshold, and
@@ -621,7 +635,7 @@ inline void lidar_launch(hipStream_t s, const FrameCam& C, const dsr_lidar_param
   hipLaunchKernelGGL(k_lidar_scan, dim3(nd), dim3(FRAME_WG), 0, s, P, (const LidarDet*)D.dets, nc, (const int*)D.cnt,
                      D.coff, D.hits, D.nproj, D.recs);
   if (nc > 0)
-    hipLaunchKernelGGL(k_lidar_emit, dim3(gc, nd), dim3(FRAME_WG), 0, s, C, P, X, (const float*)D.velo, S.n_velo,
+    hipLaunchKernelGGL(k_lidar_emit<true>, dim3(gc, nd), dim3(FRAME_WG), 0, s, C, P, X, (const float*)D.velo, S.n_velo,
                        S.stride, (const int*)D.inst, (const dsr_lidar_mask*)D.masks, n_masks, (const LidarDet*)D.dets,
                        nc, (const int*)D.cnt, (const int*)D.coff, (const dsr_lidar_det_out*)D.recs, D.hits, D.nproj,
                        (const ObjDesc*)desc, pts, rays, dobs);

@@ -6,7 +6,8 @@
  *   dsr_c_stress               no-device paths: ABI version, argument validation and error
  *                              reporting of every entry point that checks its arguments before
  *                              touching the device, the host rules (dsr_scene_bin_host,
- *                              dsr_lidar_inputs_host) on hand-computed inputs, context creation
+ *                              dsr_lidar_inputs_host, dsr_lidar_track_prep_host) on hand-computed
+ *                              inputs, context creation
  *                              (-3 without a device)
  *   dsr_c_stress <dir>         the same inputs as dsr_c_smoke (weights.f32, params.f32,
  *                              objects.bin), then every device entry point with cross-checks:
@@ -20,7 +21,9 @@
  *                              ample and too small totals, n = 0) against it, scene queries
  *                              (dsr_scene_*) against sdf_eval and their records, the LiDAR
  *                              ingest (dsr_lidar_inputs against a hand-computed sweep and the
- *                              host rule, dsr_batch_refill_lidar against dsr_batch_refill), forced audit
+ *                              host rule, dsr_batch_refill_lidar against dsr_batch_refill), the
+ *                              resident tracker (dsr_tracker_* from the same sweep and from host
+ *                              rows against dsr_pose_only_batch), forced audit
  *                              violations and their spare-iteration redo (test hooks), and the
  *                              error paths of a live context.  Exit status 0 = every check held.
  */
@@ -213,6 +216,30 @@ static void lidar_no_device_paths(void) {
   CHECK(dsr_batch_refill_lidar(NULL, &s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 1, &s.det) < 0,
         "refill_lidar(NULL) accepted");
   CHECK(dsr_batch_lidar_info(NULL, &o) < 0, "lidar_info(NULL) accepted");
+  /* the tracker's start pose on the same detection: t_cam_velo [R | o] = the t_cam_obj above without
+     its scale, and the scale beside it; then the tracker's calls without a handle */
+  float tse3[16], dscale = 0.f;
+  CHECK(dsr_lidar_track_prep_host(&s.par, s.tcv, 1, &s.det, tse3, &dscale) == 0, "lidar_track_prep_host failed");
+  CHECK(tse3[2] == 1.f && tse3[5] == -1.f && tse3[8] == 1.f && tse3[11] == 8.f && tse3[0] == 0.f && tse3[3] == 0.f &&
+            tse3[7] == 0.f && tse3[12] == 0.f && tse3[15] == 1.f && dscale == 1.1f * 2.f,
+        "track prep %g %g %g %g scale %g", tse3[2], tse3[5], tse3[8], tse3[11], dscale);
+  CHECK(dsr_lidar_track_prep_host(NULL, s.tcv, 1, &s.det, tse3, &dscale) < 0, "track prep: NULL params accepted");
+  CHECK(dsr_lidar_track_prep_host(&s.par, NULL, 1, &s.det, tse3, &dscale) < 0, "track prep: NULL t_cam_velo accepted");
+  CHECK(dsr_lidar_track_prep_host(&s.par, s.tcv, 1, NULL, tse3, &dscale) < 0, "track prep: NULL detections accepted");
+  CHECK(dsr_lidar_track_prep_host(&s.par, s.tcv, 1, &s.det, NULL, &dscale) < 0, "track prep: NULL pose array accepted");
+  CHECK(dsr_lidar_track_prep_host(&s.par, s.tcv, 1, &s.det, tse3, NULL) < 0, "track prep: NULL scale array accepted");
+  CHECK(dsr_lidar_track_prep_host(&s.par, s.tcv, -1, &s.det, tse3, &dscale) < 0, "track prep: n_det -1 accepted");
+  CHECK(dsr_lidar_track_prep_host(&s.par, s.tcv, 0, NULL, NULL, NULL) == 0, "track prep: no detections refused");
+  {
+    dsr_tracker* tr = NULL;
+    dsr_track_out trec;
+    dsr_track_det pri = {1.f, 0, {0}};
+    CHECK(dsr_tracker_create(NULL, NULL, NULL, 1, 1, &tr) < 0 && tr == NULL, "tracker_create(NULL ctx) accepted");
+    CHECK(dsr_tracker_track(NULL, 1, NULL) < 0, "tracker_track(NULL) accepted");
+    CHECK(dsr_tracker_track_lidar(NULL, &s.par, s.tcv, &s.velo[0][0], 10, 4, 1, &s.det, &pri) < 0, "tracker_track_lidar(NULL) accepted");
+    CHECK(dsr_tracker_query(NULL) < 0 && dsr_tracker_download(NULL, tse3, &trec) < 0, "tracker query / download(NULL) accepted");
+    CHECK(dsr_tracker_destroy(NULL) == 0, "tracker_destroy(NULL)");
+  }
 }
 
 /* argument validation that needs no device (the CPU-container case) */
@@ -727,6 +754,63 @@ int main(int argc, char** argv) {
     CHECK(same_out(lo, fo, 2), "lidar: sweep refill differs from the host arrays' refill");
     CHECK(!lo[1].is_good, "lidar: an empty object converged");
     CHECK(dsr_batch_destroy(bt) == 0, "destroy");
+  }
+
+  /* resident tracker: a sweep call and a host-row call against dsr_pose_only_batch on the host
+     rule's rows, 6 pose-only iterations (the iteration-4 filter runs) */
+  if (run_section("track")) {
+    lidar_scene s;
+    lidar_scene_make(&s);
+    s.par.max_pts = 5;
+    s.par.max_bg = 0;
+    float code[64] = {0.f};
+    dsr_lidar_det dets[2] = {s.det, s.det};
+    dets[0].code = dets[1].code = code;
+    dets[1].trans[0] = -8.f;                        /* its box holds no sweep point */
+    float hp[2][15], hr[2][15], hz[2][5], tse3[2][16], dscale[2], want[2][16], got[2][16];
+    dsr_lidar_det_out ho[2];
+    dsr_track_out recs[2];
+    memset(hp, 0, sizeof hp), memset(hr, 0, sizeof hr), memset(hz, 0, sizeof hz);
+    CHECK(dsr_lidar_inputs_host(&s.cam, &s.par, s.tcv, &s.velo[0][0], 10, 4, s.inst, 2, s.masks, 2, dets, &hp[0][0],
+                                &hr[0][0], &hz[0][0], ho) == 0, "lidar_inputs_host failed");
+    CHECK(dsr_lidar_track_prep_host(&s.par, s.tcv, 2, dets, &tse3[0][0], dscale) == 0, "lidar_track_prep_host failed");
+    dsr_optim_params q = p;
+    q.pose_only_iterations = 6;
+    dsr_pose_in pin[3];
+    dsr_track_det pri[2];
+    memset(pri, 0, sizeof pri);
+    for (int d = 0; d < 2; ++d) {
+      memcpy(pin[d].t_co_se3, tse3[d], sizeof tse3[d]);
+      pin[d].scale = pri[d].scale = dscale[d];
+      pin[d].pts = hp[d], pin[d].n_pts = ho[d].n_pts, pin[d].code = code;
+    }
+    pin[2] = pin[0];
+    CHECK(dsr_pose_only_batch(ctx, dec, &q, 2, pin, &want[0][0]) == 0, "%s", dsr_last_error(ctx));
+    dsr_tracker* tr = NULL;
+    CHECK(dsr_tracker_create(ctx, dec, &q, 2, 8, &tr) == 0, "%s", dsr_last_error(ctx));
+    CHECK(dsr_tracker_query(tr) < 0 && dsr_tracker_download(tr, &got[0][0], recs) < 0, "tracker: results before a call");
+    CHECK(dsr_tracker_track_lidar(tr, &s.par, s.tcv, &s.velo[0][0], 10, 4, 2, dets, pri) == 0, "%s", dsr_last_error(ctx));
+    int fin = 0;
+    while ((fin = dsr_tracker_query(tr)) == 0) {}
+    CHECK(fin == 1, "tracker_query %d: %s", fin, dsr_last_error(ctx));
+    CHECK(dsr_tracker_download(tr, &got[0][0], recs) == 0, "%s", dsr_last_error(ctx));
+    CHECK(memcmp(want, got, sizeof want) == 0, "tracker: sweep call differs from pose_only_batch");
+    CHECK(recs[0].n_near == 8 && recs[0].n_crop == 5 && recs[0].n_pts == 5 && recs[0].n_inliers <= 5 &&
+              recs[1].status == DSR_TRACK_NO_POINTS && recs[1].n_crop == 0 && got[1][0] != got[1][0],
+          "tracker records %d %d %d %d", recs[0].n_near, recs[0].n_crop, recs[0].n_pts, recs[1].status);
+    memset(got, 0, sizeof got);
+    CHECK(dsr_tracker_track(tr, 2, pin) == 0 && dsr_tracker_download(tr, &got[0][0], NULL) == 0, "%s", dsr_last_error(ctx));
+    CHECK(memcmp(want, got, sizeof want) == 0, "tracker: host rows differ from pose_only_batch");
+    CHECK(dsr_tracker_track(tr, 3, pin) < 0 && dsr_tracker_track(tr, 0, pin) < 0, "tracker: n_obj outside 1 .. max_obj accepted");
+    s.par.max_pts = 9;
+    CHECK(dsr_tracker_track_lidar(tr, &s.par, s.tcv, &s.velo[0][0], 10, 4, 2, dets, pri) < 0, "tracker: max_pts 9 > 8 accepted");
+    s.par.max_pts = 5;
+    pri[1].scale = 0.f;
+    CHECK(dsr_tracker_track_lidar(tr, &s.par, s.tcv, &s.velo[0][0], 10, 4, 2, dets, pri) < 0 &&
+              strlen(dsr_last_error(ctx)) > 0, "tracker: scale 0 accepted");
+    CHECK(dsr_tracker_track(tr, 1, pin) == 0 && dsr_tracker_download(tr, &got[0][0], NULL) == 0, "%s", dsr_last_error(ctx));
+    CHECK(memcmp(want[0], got[0], sizeof want[0]) == 0, "tracker: wrong bits after refused calls");
+    CHECK(dsr_tracker_destroy(tr) == 0, "tracker_destroy");
   }
 
   /* graph capture and replays */

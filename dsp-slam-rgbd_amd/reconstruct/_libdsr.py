@@ -245,6 +245,22 @@ LIDAR_STATUS = {0: "ok", 1: "behind the camera", 2: "no sweep point in the box",
                 3: "no mask holds more than half of the projected points", 4: "mask of at most min_mask_area pixels"}
 
 
+class TrackOut(C.Structure):
+    """dsr_track_out: the record of one tracked object."""
+    _fields_ = [("status", C.c_int), ("n_pts", C.c_int), ("n_inliers", C.c_int), ("n_near", C.c_int),
+                ("n_crop", C.c_int)]
+
+
+class TrackDet(C.Structure):
+    """dsr_track_det: the map object's scale and, with ``pose_given``, the start pose of a detection
+    tracked from a sweep."""
+    _fields_ = [("scale", C.c_float), ("pose_given", C.c_int), ("t_co_se3", C.c_float * 16)]
+
+
+TRACK_OK, TRACK_NO_POINTS, TRACK_NO_INLIERS = 0, 1, 2   # include/dsr.h DSR_TRACK_*
+TRACK_STATUS = {0: "ok", 1: "no points", 2: "the inlier filter kept no point"}
+
+
 #: dsr_batch_lite_diag record layout (csrc/dsr_dev.hpp: STD_*)
 LITE_DIAG_FIELDS = ("broken_blocks", "recorded", "block", "wave", "counter", "target", "observed", "tile_iter",
                     "hw_id", "xcc_id", "polls", "real_ticks")
@@ -344,6 +360,15 @@ SIGNATURES = {
     "dsr_batch_refill_lidar": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(LidarParams), FP, FP, C.c_int,
                                          C.c_int, IP, C.c_int, C.POINTER(LidarMask), C.c_int, C.POINTER(LidarDet)]),
     "dsr_batch_lidar_info": (C.c_int, [C.c_void_p, C.POINTER(LidarDetOut)]),
+    "dsr_tracker_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimParams), C.c_int, C.c_int,
+                                     C.POINTER(C.c_void_p)]),
+    "dsr_tracker_destroy": (C.c_int, [C.c_void_p]),
+    "dsr_tracker_track": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PoseIn)]),
+    "dsr_tracker_track_lidar": (C.c_int, [C.c_void_p, C.POINTER(LidarParams), FP, FP, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(LidarDet), C.POINTER(TrackDet)]),
+    "dsr_tracker_query": (C.c_int, [C.c_void_p]),
+    "dsr_tracker_download": (C.c_int, [C.c_void_p, FP, C.POINTER(TrackOut)]),
+    "dsr_lidar_track_prep_host": (C.c_int, [C.POINTER(LidarParams), FP, C.c_int, C.POINTER(LidarDet), FP, FP]),
 }
 
 #: entry points added without an ABI number change: callers detect them by the symbol, so a
@@ -354,7 +379,9 @@ BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_rende
              "dsr_scene_set_objects", "dsr_scene_query", "dsr_scene_peek", "dsr_scene_stats_get", "dsr_scene_destroy",
              "dsr_scene_bin_host", "dsr_frame_pose_params_default", "dsr_frame_poses_host", "dsr_frame_poses",
              "dsr_batch_refill_frame_poses", "dsr_batch_frame_pose_info", "dsr_lidar_params_default",
-             "dsr_lidar_inputs_host", "dsr_lidar_inputs", "dsr_batch_refill_lidar", "dsr_batch_lidar_info")
+             "dsr_lidar_inputs_host", "dsr_lidar_inputs", "dsr_batch_refill_lidar", "dsr_batch_lidar_info",
+             "dsr_tracker_create", "dsr_tracker_destroy", "dsr_tracker_track", "dsr_tracker_track_lidar",
+             "dsr_tracker_query", "dsr_tracker_download", "dsr_lidar_track_prep_host")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

@@ -25,6 +25,9 @@ runs in libdsr's HIP kernels on an MI355X (``include/dsr.h``):
 * ``Optimizer.compute_sdf_loss_objectpoint_zhjd(pts_obj, code)`` —
   optimizer.py:207-213 -> ``dsr_sdf_eval``.
 * ``Optimizer.estimate_pose_cam_obj(...)`` — optimizer.py:46-87 -> ``dsr_pose_only``.
+* ``Optimizer.track_objects([...])`` / ``track_lidar_frame(...)`` — NEW: the per-detection
+  ``estimate_pose_cam_obj`` loop of LocalMapping_util.cc:103-110 through a resident
+  ``reconstruct.tracker.ObjectTracker`` -> ``dsr_tracker_*``.
 * ``MeshExtractor`` — optimizer.py:216-233 -> ``dsr_mesher_*`` (grid decode and
   marching cubes on device).
 
@@ -558,6 +561,47 @@ class Optimizer(object):
         ctx.check(ctx.lib.dsr_pose_only_batch(ctx.handle, self.decoder.handle, C.byref(self.params), n,
                                               ins, L.fptr(out)), "dsr_pose_only_batch")
         return [out[i] for i in range(n)]
+
+    def _tracker_for(self, n_obj, n_pts):
+        """The optimizer's one ``ObjectTracker``, recreated larger when a call does not fit."""
+        from reconstruct.tracker import ObjectTracker
+
+        tr = getattr(self, "_tracker", None)
+        if tr is None or tr._h is None or not tr.fits(n_obj, n_pts):
+            pad = lambda v, m: -(-max(v, 1) // m) * m  # noqa: E731
+            cn, cp = pad(n_obj, 8), pad(n_pts, 64)
+            if tr is not None:
+                cn, cp = max(cn, tr.max_obj), max(cp, tr.max_pts)
+                tr.close()
+            tr = self._tracker = ObjectTracker(self, cn, cp)
+        return tr
+
+    def track_objects(self, objects):
+        """``estimate_pose_cam_obj_batch`` through the optimizer's resident ``ObjectTracker``
+        (reconstruct/tracker.py): the loop of
+        LocalMapping::GetNewObservations_onyforStereo (LocalMapping_util.cc:103-110) as one call
+        without per-call allocation or a host step inside the GN loop.  Returns ``(poses,
+        records)``; the poses are bitwise those of ``estimate_pose_cam_obj_batch``."""
+        n = len(objects)
+        if n == 0:
+            return [], []
+        tr = self._tracker_for(n, max(_f32(ob[2], 3).shape[0] for ob in objects))
+        tr.track(objects)
+        return tr.result()
+
+    def track_lidar_frame(self, velo, t_cam_velo, detections, priors, **params):
+        """The same from a Velodyne sweep: every detection's surface points are cropped on the
+        device (the rows of ``utils.lidar_inputs``) and tracked without coming back to the host.
+        ``detections``, ``priors`` and ``params`` (max_pts, radius, box_margin): see
+        ``ObjectTracker.track_lidar``.  Returns ``(poses, records)``."""
+        from reconstruct import utils as U
+
+        n = len(detections)
+        if n == 0:
+            return [], []
+        tr = self._tracker_for(n, U.lidar_params(**params).max_pts)
+        tr.track_lidar(velo, t_cam_velo, detections, priors, params)
+        return tr.result()
 
     def reconstruct_objects_multi(self, objects, decoders, return_path=False):
         """``reconstruct_objects`` spread over several devices from ONE process

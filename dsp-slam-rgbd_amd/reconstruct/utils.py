@@ -455,6 +455,25 @@ def lidar_inputs(velo, instance, masks, detections, camera, t_cam_velo, **params
     return objects, records
 
 
+def lidar_track_prep(detections, t_cam_velo, **params):
+    """The start poses of detections tracked from a sweep (``dsr_lidar_track_prep_host``: plain C++
+    on the host, no device): per detection the SE(3) ``t_co_se3`` (n, 4, 4) =
+    t_cam_velo [R | o] and ``det_scale`` (n,) = box_margin l / 2 — ObjectDetection's decomposition of
+    the ingest's t_cam_obj (src/ObjectDetection.cc:29-37).  ``params``: ``box_margin``."""
+    from reconstruct import _libdsr as L
+
+    p = lidar_params(**params)
+    tcv = np.ascontiguousarray(np.asarray(t_cam_velo, np.float32).reshape(16))
+    n = len(detections)
+    dets, keep = lidar_dets(detections)
+    t = np.zeros((max(n, 1), 4, 4), np.float32)
+    sc = np.zeros(max(n, 1), np.float32)
+    rc = L.load_library().dsr_lidar_track_prep_host(p, L.fptr(tcv), n, dets, L.fptr(t), L.fptr(sc))
+    if rc != 0:
+        raise L.DsrError(f"dsr_lidar_track_prep_host failed ({rc}): bad detections, t_cam_velo or box_margin")
+    return t[:n], sc[:n]
+
+
 def create_voxel_grid(vol_dim=128):
     """utils.py:97-116.  Note the reference's ``LongTensor / vol_dim`` is TRUE division
     in torch >= 1.6 (fp32), so its x/y columns are not integer lattice indices; this

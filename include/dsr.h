@@ -885,6 +885,79 @@ typedef struct {
 int dsr_pose_only_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p,
                         int n_obj, const dsr_pose_in* in, float* t_out);
 
+/* ---- resident object tracker: dsr_pose_only_batch as a handle.  Replaces the
+ * loop of LocalMapping::GetNewObservations_onyforStereo (src/LocalMapping_util.cc:84-154), which
+ * calls Optimizer.estimate_pose_cam_obj (reconstruct/optimizer.py:46-87) once per detection that
+ * is associated with a map object, passing the detection's SE(3) pose, the map object's scale and
+ * code and the detection's LiDAR surface points.  The handle owns every device block and the
+ * pinned staging of a run from its creation; a call stages its inputs, enqueues everything on the
+ * context stream — descriptors, tile table and the iteration-4 inlier filter (optimizer.py:77-79)
+ * are device kernels, csrc/dsr_track.hpp — and returns; nothing between the staged upload and
+ * the final copy into the pinned block waits on the host.  The poses are bitwise those of
+ * dsr_pose_only_batch.  Callers detect these entry points by symbol; the ABI number is unchanged. */
+typedef struct dsr_tracker dsr_tracker;
+enum {
+  DSR_TRACK_OK = 0,
+  DSR_TRACK_NO_POINTS = 1,        /* n_pts == 0: the reference's J^T J / 0, a NaN pose */
+  DSR_TRACK_NO_INLIERS = 2        /* the filter kept nothing (optimizer.py:77-79): a NaN pose */
+};
+typedef struct {
+  int status;                     /* DSR_TRACK_* */
+  int n_pts;                      /* points the GN started with */
+  int n_inliers;                  /* points the filter kept; n_pts when it does not run (optimizer.py:77) */
+  int n_near, n_crop;             /* a sweep call: the ingest's counts (dsr_lidar_det_out); host rows: 0 */
+} dsr_track_out;
+typedef struct {
+  float scale;                    /* the map object's scale (pMO->scale, LocalMapping_util.cc:110) */
+  int pose_given;                 /* != 0: t_co_se3 is the start pose (e.g. Tcw Two of :106) */
+  float t_co_se3[16];             /* SE(3) camera<-object; read only with pose_given */
+} dsr_track_det;
+/* A tracker of at most max_obj objects x max_pts points per call, for the decoder and the
+ * pose-only settings of p (pose_only_iterations, code_len; optimizer.py:46-87).  Nothing but the
+ * sweep block of dsr_tracker_track_lidar (it grows with the largest sweep seen) is allocated
+ * after this call.  Errors: a null argument, max_obj < 1, max_pts outside 1 .. 2^20, max_obj x
+ * max_pts above 2^22, a code_len mismatch. */
+int dsr_tracker_create(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p, int max_obj,
+                       int max_pts, dsr_tracker** out);
+/* Waits for the context stream, then frees the handle's blocks. */
+int dsr_tracker_destroy(dsr_tracker* tr);
+/* estimate_pose_cam_obj (optimizer.py:46-87) for n_obj objects given as host rows — the loop of
+ * LocalMapping_util.cc:103-110 as one call — enqueued on the context stream; a call made while
+ * the previous one is in flight is ordered after it.  Errors, returned before the device is
+ * touched (the handle stays usable): a null argument, n_obj outside 1 .. max_obj, an object with
+ * n_pts < 0 or > max_pts, a scale that is not positive and finite, a non-finite pose. */
+int dsr_tracker_track(dsr_tracker* tr, int n_obj, const dsr_pose_in* in);
+/* The same from a sweep: detection i's points are the rows DESIGN.md 3.5d gives it (the cube and
+ * widened-box crop, the integer sel, q = t_cam_velo p; kitti_sequence.py:118-146), written by the
+ * ingest's crop kernels into the tracker's point block; association, masks, background rays and
+ * the camera play no part (the reference tracks a detection whether or not a mask matched,
+ * LocalMapping_util.cc:103-110).  Of params only max_pts (<= the tracker's), radius and
+ * box_margin are read; dets[i].code is the map object's code; prior[i] carries its scale and
+ * optionally a start pose — without one the start pose is dsr_lidar_track_prep_host's
+ * (det->SE3Tco, src/ObjectDetection.cc:29-37).  Errors, returned before the device is touched: a
+ * null argument, n_det outside 1 .. max_obj, those of dsr_lidar_inputs_host for the fields that
+ * are read, a scale that is not positive and finite, a non-finite given pose. */
+int dsr_tracker_track_lidar(dsr_tracker* tr, const dsr_lidar_params* params, const float* t_cam_velo,
+                            const float* velo, int n_velo, int stride, int n_det, const dsr_lidar_det* dets,
+                            const dsr_track_det* prior);
+/* 1: the last call has finished, 0: still in flight (as dsr_batch_query), < 0: an error. */
+int dsr_tracker_query(dsr_tracker* tr);
+/* Waits for the last call and writes its poses (t_out: n x 16, the rotation block divided by the
+ * scale, optimizer.py:84-85; NaN for an object that is not DSR_TRACK_OK) and, unless rec is NULL,
+ * its n records. */
+int dsr_tracker_download(dsr_tracker* tr, float* t_out, dsr_track_out* rec);
+/* Host only — no context, no device: the start pose of a sweep call without a given one, the
+ * decomposition of the ingest's t_cam_obj that ObjectDetection computes with a determinant and a
+ * cube root (src/ObjectDetection.cc:29-37).  With dsr_lidar_inputs_host's quantities and
+ * arithmetic (fp64 on the fp32 inputs, every operation rounded on its own, every stored value
+ * rounded to fp32 once): t_co_se3[i] (n_det x 16) = t_cam_velo [R | o], each entry the
+ * left-to-right sum DESIGN.md 3.5d gives for t_cam_obj with sigma left out, last row 0 0 0 1;
+ * det_scale[i] = (float)sigma, sigma = m l / 2.  Of params only box_margin is read.  Returns < 0
+ * for a null argument, n_det < 0 and dsr_lidar_inputs_host's errors for box_margin, t_cam_velo
+ * and the detections. */
+int dsr_lidar_track_prep_host(const dsr_lidar_params* params, const float* t_cam_velo, int n_det,
+                              const dsr_lidar_det* dets, float* t_co_se3, float* det_scale);
+
 #ifdef __cplusplus
 }
 #endif
