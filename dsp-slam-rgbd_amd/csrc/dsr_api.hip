@@ -1806,7 +1806,8 @@ struct IngestCall {
 // Waits until the copies recorded in up_ev have left the owner's staging buffers and the pinned
 // half of its ingest block g, then makes the block hold `up` uploaded bytes of `all` (0, 0: a fill
 // without one).  Both halves only grow; the device block is replaced only once no kernel can still
-// read it.  The owner is a batch (refill_begin) or a tracker (dsr_tracker_track_lidar).
+// read it.  The owner is a batch (refill_begin) or a tracker (dsr_tracker_track_lidar,
+// dsr_tracker_track_frame).
 static int ingest_fit(dsr_ctx* ctx, dsr_batch::IngestBlock& g, hipEvent_t up_ev, size_t up, size_t all) {
   DSR_CHECK(ctx, hipEventSynchronize(up_ev));
   if (up > g.host_bytes) {
@@ -4393,6 +4394,7 @@ struct dsr_tracker {
   char* host = nullptr;
   size_t head_bytes = 0, pts_bytes = 0, tail_bytes = 0;
   dsr_batch::IngestBlock sweep;      // a sweep call's block (lidar_carve without an image): it grows
+  dsr_batch::IngestBlock frame;      // a frame call's block (frame_carve): it grows
   hipEvent_t up_ev = nullptr;        // recorded after a call's uploads
   hipEvent_t done_ev = nullptr;      // recorded after a call's copy into the pinned tail
   int n_last = 0;                    // objects of the last call (0: none yet)
@@ -4414,6 +4416,8 @@ int dsr_tracker_destroy(dsr_tracker* tr) {
   if (tr->host) hipHostFree(tr->host);
   if (tr->sweep.host) hipHostFree(tr->sweep.host);
   if (tr->sweep.dev) hipFree(tr->sweep.dev);
+  if (tr->frame.host) hipHostFree(tr->frame.host);
+  if (tr->frame.dev) hipFree(tr->frame.dev);
   delete tr;
   return 0;
 }
@@ -4490,40 +4494,71 @@ static void track_stage(dsr_tracker* tr, int o, const float* t_co_se3, float sca
   tr->scale[o] = scale;
 }
 
+namespace {
+// where a call's points come from when not from host rows: a sweep (S, LP, tcv) through tr->sweep
+// or a depth image (FC, FP) through tr->frame; `up` bytes of that block are uploaded
+struct TrackIngest {
+  const LidarShape* S = nullptr;
+  const dsr_lidar_params* LP = nullptr;
+  const float* tcv = nullptr;
+  const FrameCam* FC = nullptr;
+  const dsr_frame_params* FP = nullptr;
+  size_t up = 0;
+};
+}  // namespace
+
 // Everything of a call after its staging, on the context stream: the uploads (the head, then
-// pts_floats of host rows or sweep_up bytes of the sweep block S lays out), the fill's kernels, the
-// GN loop of dsr_pose_only_batch with the filter and the tile table on the device, and the copy
-// into the pinned tail.  tile_bound: the call's tiles at most (sizes the Jacobian grid).
-static int track_run(dsr_tracker* tr, int n, size_t pts_floats, int tile_bound, const dsr_lidar_params* LP,
-                     const LidarShape* S, const float* tcv, size_t sweep_up) {
+// pts_floats of host rows or G.up bytes of the ingest block G names), the fill's kernels, the GN
+// loop of dsr_pose_only_batch with the filter and the tile table on the device, and the copy into
+// the pinned tail.  tile_bound: the call's tiles at most (sizes the Jacobian grid).
+static int track_run(dsr_tracker* tr, int n, size_t pts_floats, int tile_bound, const TrackIngest& G) {
   dsr_ctx* ctx = tr->ctx;
   hipStream_t s = ctx->stream;
+  const LidarShape* S = G.S;
   DSR_CHECK(ctx, hipMemcpyAsync(tr->head, tr->host, tr->head_bytes, hipMemcpyHostToDevice, s));
   if (pts_floats)
     DSR_CHECK(ctx, hipMemcpyAsync(tr->pts, tr->host + tr->head_bytes, sizeof(float) * pts_floats, hipMemcpyHostToDevice, s));
   LidarDev L{};
+  FrameDev F{};
   if (S) {
-    DSR_CHECK(ctx, hipMemcpyAsync(tr->sweep.dev, tr->sweep.host, sweep_up, hipMemcpyHostToDevice, s));
+    DSR_CHECK(ctx, hipMemcpyAsync(tr->sweep.dev, tr->sweep.host, G.up, hipMemcpyHostToDevice, s));
     L = lidar_carve(tr->sweep.dev, *S);
+  }
+  if (G.FC) {
+    DSR_CHECK(ctx, hipMemcpyAsync(tr->frame.dev, tr->frame.host, G.up, hipMemcpyHostToDevice, s));
+    F = frame_carve(tr->frame.dev, G.FC->W, G.FC->H, n);
   }
   DSR_CHECK(ctx, hipEventRecord(tr->up_ev, s));
   const int nc = S ? lidar_chunks(S->n_velo) : 0;
   const unsigned gc = (unsigned)((nc + FRAME_WAVES - 1) / FRAME_WAVES);
+  const unsigned gy = G.FC ? (unsigned)((G.FC->H + FRAME_WAVES - 1) / FRAME_WAVES) : 0;
   if (S) {                                  // the crop passes of lidar_launch; no image pass runs
     if (nc > 0)
       hipLaunchKernelGGL(k_lidar_count, dim3(gc, n), dim3(FRAME_WG), 0, s, (const float*)L.velo, S->n_velo, S->stride,
                          (const LidarDet*)L.dets, nc, L.cnt);
-    hipLaunchKernelGGL(k_lidar_scan, dim3(n), dim3(FRAME_WG), 0, s, *LP, (const LidarDet*)L.dets, nc, (const int*)L.cnt,
+    hipLaunchKernelGGL(k_lidar_scan, dim3(n), dim3(FRAME_WG), 0, s, *G.LP, (const LidarDet*)L.dets, nc, (const int*)L.cnt,
                        L.coff, L.hits, L.nproj, L.recs);
   }
+  if (G.FC) {                               // the first two passes of frame_launch; max_bg = 0: no background
+    hipLaunchKernelGGL(k_frame_rows, dim3(gy, n), dim3(FRAME_WG), 0, s, *G.FC, *G.FP, (const float*)F.depth,
+                       (const int*)F.inst, (const FrameDet*)F.dets, F.rows);
+    hipLaunchKernelGGL(k_frame_scan, dim3(n), dim3(FRAME_WG), 0, s, *G.FC, *G.FP, (const int*)F.inst,
+                       (const FrameDet*)F.dets, (const int4*)F.rows, F.voff, F.bgoff, F.aux, F.recs, (ObjDesc*)nullptr);
+  }
   hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(TILE_SCAN_THREADS), 0, s, n, tr->max_pts, tr->tpo, (const int*)tr->cnt,
-                     (const dsr_lidar_det_out*)(S ? L.recs : nullptr), tr->desc, tr->recs, tr->tiles, tr->n_tiles);
+                     (const dsr_lidar_det_out*)(S ? L.recs : nullptr), (const dsr_frame_det_out*)(G.FC ? F.recs : nullptr),
+                     tr->desc, tr->recs, tr->tiles, tr->n_tiles);
   if (S && nc > 0)
-    hipLaunchKernelGGL(k_lidar_emit<false>, dim3(gc, n), dim3(FRAME_WG), 0, s, FrameCam{}, *LP, lidar_xf(tcv),
+    hipLaunchKernelGGL(k_lidar_emit<false>, dim3(gc, n), dim3(FRAME_WG), 0, s, FrameCam{}, *G.LP, lidar_xf(G.tcv),
                        (const float*)L.velo, S->n_velo, S->stride, (const int*)nullptr, (const dsr_lidar_mask*)nullptr, 0,
                        (const LidarDet*)L.dets, nc, (const int*)L.cnt, (const int*)L.coff,
                        (const dsr_lidar_det_out*)L.recs, (int*)nullptr, (int*)nullptr, (const ObjDesc*)tr->desc, tr->pts,
                        (float*)nullptr, (float*)nullptr);
+  if (G.FC)                                 // the points alone, without the background z-slice
+    hipLaunchKernelGGL(k_frame_emit<false>, dim3(gy, n), dim3(FRAME_WG), 0, s, *G.FC, *G.FP, (const float*)F.depth,
+                       (const int*)F.inst, (const FrameDet*)F.dets, (const int4*)F.rows, (const int*)F.voff,
+                       (const int*)F.bgoff, (const int*)F.aux, (const dsr_frame_det_out*)F.recs,
+                       (const ObjDesc*)tr->desc, tr->pts, (float*)nullptr, (float*)nullptr);
   const DevDecoder& D = tr->dec->D;
   fold_codes(s, D, tr->z, n, tr->b0, tr->b4);
   hipLaunchKernelGGL(k_init_state, dim3(n), dim3(64), 0, s, n, (const float*)tr->t_in, (const int*)tr->is_oc,
@@ -4578,7 +4613,7 @@ int dsr_tracker_track(dsr_tracker* tr, int n_obj, const dsr_pose_in* in) {
   }
   // objects 0 .. n_obj - 1 at the fixed stride: up to the last object's last row
   const size_t up = ((size_t)(n_obj - 1) * tr->max_pts + in[n_obj - 1].n_pts) * 3;
-  return track_run(tr, n_obj, tiles ? up : 0, (int)tiles, nullptr, nullptr, nullptr, 0);
+  return track_run(tr, n_obj, tiles ? up : 0, (int)tiles, TrackIngest{});
 }
 
 // dsr_lidar_inputs_host's argument errors for what a tracker call reads: the fields that are not
@@ -4630,7 +4665,49 @@ int dsr_tracker_track_lidar(dsr_tracker* tr, const dsr_lidar_params* params, con
     track_stage(tr, o, prior[o].pose_given ? prior[o].t_co_se3 : t, prior[o].scale, dets[o].code, 0);
   }
   const int tiles = n_det * track_tiles_per_obj(params->max_pts);
-  return track_run(tr, n_det, 0, tiles, params, &S, t_cam_velo, up);
+  TrackIngest G;
+  G.S = &S; G.LP = params; G.tcv = t_cam_velo; G.up = up;
+  return track_run(tr, n_det, 0, tiles, G);
+}
+
+// The same from a depth image and its instance labels: the ingest's row passes (k_frame_rows,
+// k_frame_scan) and k_frame_emit<false> write detection i's surface points into
+// the tracker's point block.  The fields that are not read are given valid values before
+// dsr_frame_inputs_host's argument check (no background grid, the mask's tight box, no pose).
+int dsr_tracker_track_frame(dsr_tracker* tr, const dsr_camera* cam, const dsr_frame_params* params,
+                            const float* depth, const int* instance, int n_det, const dsr_frame_det* dets,
+                            const dsr_track_det* prior) {
+  if (!tr) return -2;
+  dsr_ctx* ctx = tr->ctx;
+  if (!cam || !params || !depth || !instance || !dets || !prior) return fail(ctx, "null argument");
+  if (n_det < 1 || n_det > tr->max_obj) return fail(ctx, "tracker: n_det must be in [1, the tracker's max_obj]");
+  const dsr_frame_params Q{params->max_pts, 0, 1, 0, params->min_mask_area, params->near, params->far};
+  std::vector<dsr_frame_det> read(n_det);
+  for (int o = 0; o < n_det; ++o) {
+    read[o] = dsr_frame_det{};
+    read[o].label = dets[o].label;
+    read[o].bbox[2] = read[o].bbox[3] = -1;
+    read[o].code = dets[o].code;
+  }
+  if (const char* m = frame_args_error(cam, &Q, depth, instance, n_det, read.data())) return fail(ctx, m);
+  if (Q.max_pts > tr->max_pts) return fail(ctx, "tracker: max_pts exceeds the tracker's max_pts");
+  for (int o = 0; o < n_det; ++o) {
+    if (!read[o].code) return fail(ctx, "null argument");
+    if (!prior[o].pose_given) return fail(ctx, "tracker: a frame call needs a start pose (pose_given)");
+    if (!track_pose_ok(prior[o].t_co_se3, prior[o].scale))
+      return fail(ctx, "tracker: scale must be positive and finite, the pose finite");
+  }
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const int W = cam->width, H = cam->height;
+  const size_t up = frame_upload_bytes(W, H, n_det);
+  if (int rc = ingest_fit(ctx, tr->frame, tr->up_ev, up, frame_dev_bytes(W, H, n_det))) return rc;
+  frame_pack(tr->frame.host, cam, depth, instance, n_det, read.data());
+  for (int o = 0; o < n_det; ++o) track_stage(tr, o, prior[o].t_co_se3, prior[o].scale, read[o].code, 0);
+  const FrameCam FC = frame_cam(cam);
+  TrackIngest G;
+  G.FC = &FC; G.FP = &Q; G.up = up;
+  return track_run(tr, n_det, 0, n_det * track_tiles_per_obj(Q.max_pts), G);
 }
 
 int dsr_tracker_query(dsr_tracker* tr) {

@@ -305,6 +305,9 @@ __global__ __launch_bounds__(FRAME_WG) void k_frame_scan(FrameCam C, dsr_frame_p
 // (ceil(H / FRAME_WAVES), n_det, 2), one wave per image / grid row.  Outputs go to the slots of
 // desc (a capacity batch) or, desc == null, to fixed strides per detection (max_pts x 3,
 // (max_pts + max_bg) x 3, max_pts); only a batch's dobs has rows for the background rays (0).
+// RAYS = false (the tracker, dsr_track.hpp): the surface points alone, through desc's pts_off —
+// launched without the background z-slice; rays, dobs, bgoff and aux are not read.
+template <bool RAYS>
 __global__ __launch_bounds__(FRAME_WG) DSR_NO_PK_F32 void k_frame_emit(FrameCam C, dsr_frame_params P,
                                                          const float* __restrict__ depth,
                                                          const int* __restrict__ inst,
@@ -318,15 +321,19 @@ __global__ __launch_bounds__(FRAME_WG) DSR_NO_PK_F32 void k_frame_emit(FrameCam 
   const int lane = threadIdx.x & 63, j = blockIdx.x * FRAME_WAVES + (threadIdx.x >> 6), d = blockIdx.y;
   const dsr_frame_det_out& rec = recs[d];
   if (rec.status != DSR_FRAME_OK) return;
-  float *op, *orr, *oz;
+  float *op, *orr = nullptr, *oz = nullptr;
   if (desc) {
     op = pts + (size_t)desc[d].pts_off * 3;
-    orr = rays + (size_t)desc[d].ray_off * 3;
-    oz = dobs + desc[d].ray_off;
+    if constexpr (RAYS) {
+      orr = rays + (size_t)desc[d].ray_off * 3;
+      oz = dobs + desc[d].ray_off;
+    }
   } else {
     op = pts + (size_t)d * P.max_pts * 3;
-    orr = rays + (size_t)d * ((size_t)P.max_pts + P.max_bg) * 3;
-    oz = dobs + (size_t)d * P.max_pts;
+    if constexpr (RAYS) {
+      orr = rays + (size_t)d * ((size_t)P.max_pts + P.max_bg) * 3;
+      oz = dobs + (size_t)d * P.max_pts;
+    }
   }
   const int label = dets[d].label;
   const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -351,14 +358,16 @@ __global__ __launch_bounds__(FRAME_WG) DSR_NO_PK_F32 void k_frame_emit(FrameCam 
         if (i >= 0 && i < n) {
           float rx, ry;
           frame_ray(C, u, v, &rx, &ry);
-          orr[i * 3] = rx; orr[i * 3 + 1] = ry; orr[i * 3 + 2] = 1.f;
+          if constexpr (RAYS) {
+            orr[i * 3] = rx; orr[i * 3 + 1] = ry; orr[i * 3 + 2] = 1.f;
+          }
           op[i * 3] = rx * z; op[i * 3 + 1] = ry * z; op[i * 3 + 2] = z;
-          oz[i] = z;
+          if constexpr (RAYS) oz[i] = z;
         }
       }
       base += __popcll(vb);
     }
-  } else {
+  } else if constexpr (RAYS) {
     const int gh = P.max_bg > 0 ? rec.grid_h : 0, gw = rec.grid_w;
     if (j >= gh) return;
     const int bl = rec.box[0], bt = rec.box[1], bw = rec.box[2] - rec.box[0] + 1, bh = rec.box[3] - rec.box[1] + 1;
@@ -431,7 +440,7 @@ inline void frame_launch(hipStream_t s, const FrameCam& C, const dsr_frame_param
                      (const int*)D.inst, (const FrameDet*)D.dets, D.rows);
   hipLaunchKernelGGL(k_frame_scan, dim3(n_det), dim3(FRAME_WG), 0, s, C, P, (const int*)D.inst,
                      (const FrameDet*)D.dets, (const int4*)D.rows, D.voff, D.bgoff, D.aux, D.recs, desc);
-  hipLaunchKernelGGL(k_frame_emit, dim3(gy, n_det, 2), dim3(FRAME_WG), 0, s, C, P, (const float*)D.depth,
+  hipLaunchKernelGGL(k_frame_emit<true>, dim3(gy, n_det, 2), dim3(FRAME_WG), 0, s, C, P, (const float*)D.depth,
                      (const int*)D.inst, (const FrameDet*)D.dets, (const int4*)D.rows, (const int*)D.voff,
                      (const int*)D.bgoff, (const int*)D.aux, (const dsr_frame_det_out*)D.recs,
                      (const ObjDesc*)desc, pts, rays, dobs);

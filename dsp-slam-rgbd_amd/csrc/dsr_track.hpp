@@ -6,6 +6,8 @@
 // (launch_jac with raw residuals, k_solve_pose, k_inv_out: dsr_kernels.hpp); what is here is what
 // that entry point does on the host between its launches: the descriptors, the tile table and the
 // iteration-4 inlier filter (optimizer.py:77-79), and the host rule of a sweep call's start pose.
+// The points come from host rows, from a sweep (k_lidar_emit<false>, dsr_lidar.hpp) or from a depth
+// image and its instance labels (k_frame_emit<false>, dsr_frame.hpp).
 //
 // Layout of a tracker of max_obj objects x max_pts points, tpo = ceil(max_pts / TILE):
 //   pts    [max_obj][max_pts][3]   object o's rows from o * max_pts           (ObjDesc.pts_off)
@@ -78,16 +80,20 @@ __device__ __forceinline__ void track_tiles(int n_obj, NOf n_of, Tile* __restric
 }
 
 // After the fill, one workgroup of TILE_SCAN_THREADS: every object's descriptor at the fixed
-// strides and its record, from the staged counts (cnt, host rows) or from where k_lidar_scan left
-// them (lrecs, a sweep: n_pts, n_near, n_crop) — no host read in between — then the tile table.
+// strides and its record, from the staged counts (cnt, host rows) or from where the ingest's scan
+// left them — k_lidar_scan (lrecs, a sweep: n_pts, n_near, n_crop) or k_frame_scan (frecs, a depth
+// image: n_pts, n_mask, n_valid; 0 points unless the ingest is ok) — no host read in between; then
+// the tile table.  At most one of lrecs and frecs is given.
 __global__ __launch_bounds__(TILE_SCAN_THREADS) void k_track_begin(int n_obj, int max_pts, int tpo,
                                                                  const int* __restrict__ cnt,
                                                                  const dsr_lidar_det_out* __restrict__ lrecs,
+                                                                 const dsr_frame_det_out* __restrict__ frecs,
                                                                  ObjDesc* __restrict__ desc,
                                                                  dsr_track_out* __restrict__ recs,
                                                                  Tile* __restrict__ tiles, int* __restrict__ n_tiles) {
+  const auto n_of = [&](int o) { return lrecs ? lrecs[o].n_pts : frecs ? frecs[o].n_pts : cnt[o]; };
   for (int o = threadIdx.x; o < n_obj; o += blockDim.x) {
-    const int n = lrecs ? lrecs[o].n_pts : cnt[o];
+    const int n = n_of(o);
     ObjDesc d;
     d.pts_off = o * max_pts; d.n_pts = n;
     d.ray_off = 0; d.n_rays = 0; d.n_fg = 0; d.cand_off = 0;
@@ -97,11 +103,11 @@ __global__ __launch_bounds__(TILE_SCAN_THREADS) void k_track_begin(int n_obj, in
     r.status = n > 0 ? DSR_TRACK_OK : DSR_TRACK_NO_POINTS;
     r.n_pts = n;
     r.n_inliers = n;
-    r.n_near = lrecs ? lrecs[o].n_near : 0;
-    r.n_crop = lrecs ? lrecs[o].n_crop : 0;
+    r.n_near = lrecs ? lrecs[o].n_near : frecs ? frecs[o].n_mask : 0;
+    r.n_crop = lrecs ? lrecs[o].n_crop : frecs ? frecs[o].n_valid : 0;
     recs[o] = r;
   }
-  track_tiles(n_obj, [&](int o) { return lrecs ? lrecs[o].n_pts : cnt[o]; }, tiles, n_tiles);
+  track_tiles(n_obj, n_of, tiles, n_tiles);
 }
 
 // After the filter: the tile table of the compacted point sets.

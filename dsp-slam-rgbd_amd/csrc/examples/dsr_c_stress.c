@@ -22,8 +22,8 @@
  *                              (dsr_scene_*) against sdf_eval and their records, the LiDAR
  *                              ingest (dsr_lidar_inputs against a hand-computed sweep and the
  *                              host rule, dsr_batch_refill_lidar against dsr_batch_refill), the
- *                              resident tracker (dsr_tracker_* from the same sweep and from host
- *                              rows against dsr_pose_only_batch), forced audit
+ *                              resident tracker (dsr_tracker_* from the same sweep, from host
+ *                              rows and from a depth image against dsr_pose_only_batch), forced audit
  *                              violations and their spare-iteration redo (test hooks), and the
  *                              error paths of a live context.  Exit status 0 = every check held.
  */
@@ -237,6 +237,7 @@ static void lidar_no_device_paths(void) {
     CHECK(dsr_tracker_create(NULL, NULL, NULL, 1, 1, &tr) < 0 && tr == NULL, "tracker_create(NULL ctx) accepted");
     CHECK(dsr_tracker_track(NULL, 1, NULL) < 0, "tracker_track(NULL) accepted");
     CHECK(dsr_tracker_track_lidar(NULL, &s.par, s.tcv, &s.velo[0][0], 10, 4, 1, &s.det, &pri) < 0, "tracker_track_lidar(NULL) accepted");
+    CHECK(dsr_tracker_track_frame(NULL, &s.cam, NULL, NULL, s.inst, 1, NULL, &pri) < 0, "tracker_track_frame(NULL) accepted");
     CHECK(dsr_tracker_query(NULL) < 0 && dsr_tracker_download(NULL, tse3, &trec) < 0, "tracker query / download(NULL) accepted");
     CHECK(dsr_tracker_destroy(NULL) == 0, "tracker_destroy(NULL)");
   }
@@ -810,6 +811,53 @@ int main(int argc, char** argv) {
               strlen(dsr_last_error(ctx)) > 0, "tracker: scale 0 accepted");
     CHECK(dsr_tracker_track(tr, 1, pin) == 0 && dsr_tracker_download(tr, &got[0][0], NULL) == 0, "%s", dsr_last_error(ctx));
     CHECK(memcmp(want[0], got[0], sizeof want[0]) == 0, "tracker: wrong bits after refused calls");
+    /* the same handle from a depth image: the 135 pixels of label 7 at z = 8 + u / 100, sub-sampled
+       to 8 rows, and an absent label, against dsr_pose_only_batch on the host rule's rows */
+    {
+      static float depth[24 * 32];
+      for (int v = 0; v < 24; ++v)
+        for (int u = 0; u < 32; ++u) depth[v * 32 + u] = 8.f + 0.01f * (float)u;
+      dsr_frame_params fp;
+      CHECK(dsr_frame_params_default(&fp) == 0, "frame_params_default");
+      fp.max_pts = 8, fp.max_bg = 0, fp.min_mask_area = 100;
+      dsr_frame_det fd[2];
+      memset(fd, 0, sizeof fd);
+      fd[0].label = 7, fd[1].label = 9;
+      fd[0].bbox[2] = fd[1].bbox[2] = -1;
+      fd[0].code = fd[1].code = code;
+      float fpts[2][24], frays[2][24], fz[2][8];
+      dsr_frame_det_out fo[2];
+      memset(fpts, 0, sizeof fpts);
+      CHECK(dsr_frame_inputs_host(&s.cam, &fp, depth, s.inst, 2, fd, &fpts[0][0], &frays[0][0], &fz[0][0], fo) == 0,
+            "frame_inputs_host failed");
+      for (int d = 0; d < 2; ++d) {
+        memcpy(pin[d].t_co_se3, tse3[0], sizeof tse3[0]);
+        memcpy(pri[d].t_co_se3, tse3[0], sizeof tse3[0]);
+        pin[d].scale = pri[d].scale = dscale[0];
+        pri[d].pose_given = 1;
+        pin[d].pts = fpts[d], pin[d].n_pts = fo[d].n_pts;
+      }
+      CHECK(dsr_pose_only_batch(ctx, dec, &q, 2, pin, &want[0][0]) == 0, "%s", dsr_last_error(ctx));
+      memset(got, 0, sizeof got);
+      CHECK(dsr_tracker_track_frame(tr, &s.cam, &fp, depth, s.inst, 2, fd, pri) == 0, "%s", dsr_last_error(ctx));
+      CHECK(dsr_tracker_download(tr, &got[0][0], recs) == 0, "%s", dsr_last_error(ctx));
+      CHECK(memcmp(want, got, sizeof want) == 0, "tracker: frame call differs from pose_only_batch");
+      CHECK(recs[0].n_near == 135 && recs[0].n_crop == 135 && recs[0].n_pts == 8 && recs[0].n_inliers <= 8 &&
+                recs[1].status == DSR_TRACK_NO_POINTS && recs[1].n_near == 0 && got[1][0] != got[1][0],
+            "tracker frame records %d %d %d %d", recs[0].n_near, recs[0].n_crop, recs[0].n_pts, recs[1].status);
+      pri[1].pose_given = 0;
+      CHECK(dsr_tracker_track_frame(tr, &s.cam, &fp, depth, s.inst, 2, fd, pri) < 0 && strlen(dsr_last_error(ctx)) > 0,
+            "tracker: a frame call without a start pose accepted");
+      pri[1].pose_given = 1;
+      fp.max_pts = 9;
+      CHECK(dsr_tracker_track_frame(tr, &s.cam, &fp, depth, s.inst, 2, fd, pri) < 0, "tracker: frame max_pts 9 > 8 accepted");
+      fd[1].code = NULL;
+      fp.max_pts = 8;
+      CHECK(dsr_tracker_track_frame(tr, &s.cam, &fp, depth, s.inst, 2, fd, pri) < 0, "tracker: a frame call with a NULL code accepted");
+      CHECK(dsr_tracker_track_frame(tr, &s.cam, &fp, depth, s.inst, 1, fd, pri) == 0 &&
+                dsr_tracker_download(tr, &got[0][0], NULL) == 0, "%s", dsr_last_error(ctx));
+      CHECK(memcmp(want[0], got[0], sizeof want[0]) == 0, "tracker: wrong bits after refused frame calls");
+    }
     CHECK(dsr_tracker_destroy(tr) == 0, "tracker_destroy");
   }
 

@@ -253,7 +253,7 @@ class TrackOut(C.Structure):
 
 class TrackDet(C.Structure):
     """dsr_track_det: the map object's scale and, with ``pose_given``, the start pose of a detection
-    tracked from a sweep."""
+    tracked from a sweep or a depth image (a frame call needs the pose)."""
     _fields_ = [("scale", C.c_float), ("pose_given", C.c_int), ("t_co_se3", C.c_float * 16)]
 
 
@@ -366,6 +366,8 @@ SIGNATURES = {
     "dsr_tracker_track": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PoseIn)]),
     "dsr_tracker_track_lidar": (C.c_int, [C.c_void_p, C.POINTER(LidarParams), FP, FP, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(LidarDet), C.POINTER(TrackDet)]),
+    "dsr_tracker_track_frame": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams), FP, IP, C.c_int,
+                                          C.POINTER(FrameDet), C.POINTER(TrackDet)]),
     "dsr_tracker_query": (C.c_int, [C.c_void_p]),
     "dsr_tracker_download": (C.c_int, [C.c_void_p, FP, C.POINTER(TrackOut)]),
     "dsr_lidar_track_prep_host": (C.c_int, [C.POINTER(LidarParams), FP, C.c_int, C.POINTER(LidarDet), FP, FP]),
@@ -381,7 +383,7 @@ BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_rende
              "dsr_batch_refill_frame_poses", "dsr_batch_frame_pose_info", "dsr_lidar_params_default",
              "dsr_lidar_inputs_host", "dsr_lidar_inputs", "dsr_batch_refill_lidar", "dsr_batch_lidar_info",
              "dsr_tracker_create", "dsr_tracker_destroy", "dsr_tracker_track", "dsr_tracker_track_lidar",
-             "dsr_tracker_query", "dsr_tracker_download", "dsr_lidar_track_prep_host")
+             "dsr_tracker_query", "dsr_tracker_download", "dsr_lidar_track_prep_host", "dsr_tracker_track_frame")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

@@ -603,6 +603,23 @@ class Optimizer(object):
         tr.track_lidar(velo, t_cam_velo, detections, priors, params)
         return tr.result()
 
+    def track_frame(self, depth, instance, detections, priors, camera, **params):
+        """The same from a depth image and an instance-label image (the RGB-D path): every
+        detection's surface points are the ``pts`` rows of ``utils.frame_inputs``, built on the
+        device and tracked without coming back to the host.  ``detections`` (``{label, code}``),
+        ``priors`` (``(scale, t_co_se3)``), ``camera`` and ``params`` (max_pts, min_mask_area,
+        near, far): see ``ObjectTracker.track_frame``.  Returns ``(poses, records)``."""
+        from reconstruct import utils as U
+
+        n = len(detections)
+        if len(priors) != n:
+            raise ValueError("one prior per detection")
+        if n == 0:
+            return [], []
+        tr = self._tracker_for(n, U.frame_params(**params).max_pts)
+        tr.track_frame(depth, instance, detections, priors, camera, params)
+        return tr.result()
+
     def reconstruct_objects_multi(self, objects, decoders, return_path=False):
         """``reconstruct_objects`` spread over several devices from ONE process
         (dsr_reconstruct_multi_ex): ``decoders`` holds one decoder handle per device (e.g.

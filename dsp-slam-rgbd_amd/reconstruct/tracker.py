@@ -5,8 +5,9 @@ The reference tracks every detection that is associated with a map object by one
 (LocalMapping::GetNewObservations_onyforStereo, src/LocalMapping_util.cc:84-154).  An
 ``ObjectTracker`` does the whole loop in one asynchronous call: its device blocks and pinned
 staging exist from its creation, the inlier filter and the tile table run on the device, and the
-points come from host rows (``track``) or straight from a Velodyne sweep (``track_lidar``).  The
-poses are bitwise those of ``Optimizer.estimate_pose_cam_obj_batch``.
+points come from host rows (``track``), straight from a Velodyne sweep (``track_lidar``) or
+straight from a depth image and its instance labels (``track_frame``).  The poses are bitwise those
+of ``Optimizer.estimate_pose_cam_obj_batch`` on the same rows.
 
 There is no CPU fallback: without libdsr / a gfx950 device the constructor raises DsrError.
 """
@@ -113,6 +114,50 @@ class ObjectTracker(object):
         ctx = self.decoder.ctx
         ctx.check(ctx.lib.dsr_tracker_track_lidar(self._handle(), p, L.fptr(tcv), L.fptr(velo), velo.shape[0],
                                                   velo.shape[1], n, dets, pri), "dsr_tracker_track_lidar")
+        self._n = n
+
+    def track_frame(self, depth, instance, detections, priors, camera, params=None):
+        """Every detection's points are its surface-point rows of the depth image, built on the
+        device (the ``pts`` rows of ``utils.frame_inputs``) — the RGB-D path,
+        which has no sweep.  ``detections``: dicts ``{label, code}``, the code the map object's;
+        ``priors``: per detection a pair ``(scale, t_co_se3)``, the map object's scale and the start
+        pose (Tcw Two, LocalMapping_util.cc:106 — there is no 3-D detector to take one from);
+        ``camera``: see ``utils.frame_camera``; ``params``: a dict of ``max_pts``,
+        ``min_mask_area``, ``near``, ``far``.  The records' ``n_near`` / ``n_crop`` hold the
+        ingest's ``n_mask`` / ``n_valid``."""
+        from reconstruct import utils as U
+        from reconstruct.optimizer import _code
+
+        n = len(detections)
+        if len(priors) != n:
+            raise ValueError("one prior per detection")
+        pri = (L.TrackDet * max(n, 1))()
+        for i, pr in enumerate(priors):
+            scale, pose = pr if isinstance(pr, (tuple, list)) else (pr, None)
+            if pose is None:
+                raise ValueError("a frame call needs every prior's start pose: (scale, t_co_se3)")
+            pri[i].scale = float(scale)
+            pri[i].pose_given = 1
+            pri[i].t_co_se3[:] = np.asarray(pose, np.float32).reshape(16).tolist()
+        unknown = set(params or {}) - {"max_pts", "min_mask_area", "near", "far"}
+        if unknown:
+            raise TypeError(f"unknown frame tracking parameters: {sorted(unknown)}")
+        p = U.frame_params(**(params or {}))
+        cam = U.frame_camera(camera)
+        depth, instance = U.frame_images(depth, instance, cam)
+        dets = (L.FrameDet * max(n, 1))()
+        keep = []
+        for i, det in enumerate(detections):
+            dets[i].label = int(det["label"])
+            code = det.get("code")
+            if code is not None:
+                keep.append(_code(code, self.code_len))
+                dets[i].code = L.fptr(keep[-1])
+        ctx = self.decoder.ctx
+        if not hasattr(ctx.lib, "dsr_tracker_track_frame"):
+            raise L.DsrError("this libdsr was built without dsr_tracker_track_frame (no fallback)")
+        ctx.check(ctx.lib.dsr_tracker_track_frame(self._handle(), cam, p, L.fptr(depth), L.iptr(instance), n, dets,
+                                                  pri), "dsr_tracker_track_frame")
         self._n = n
 
     def query(self):

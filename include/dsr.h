@@ -893,8 +893,11 @@ int dsr_pose_only_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_pa
  * pinned staging of a run from its creation; a call stages its inputs, enqueues everything on the
  * context stream — descriptors, tile table and the iteration-4 inlier filter (optimizer.py:77-79)
  * are device kernels, csrc/dsr_track.hpp — and returns; nothing between the staged upload and
- * the final copy into the pinned block waits on the host.  The poses are bitwise those of
- * dsr_pose_only_batch.  Callers detect these entry points by symbol; the ABI number is unchanged. */
+ * the final copy into the pinned block waits on the host.  The points of a call are host rows
+ * (dsr_tracker_track), or they are written on the device by an ingest's kernels from a Velodyne
+ * sweep (dsr_tracker_track_lidar) or from a depth image and its instance labels
+ * (dsr_tracker_track_frame).  The poses are bitwise those of dsr_pose_only_batch on the same rows.
+ * Callers detect these entry points by symbol; the ABI number is unchanged. */
 typedef struct dsr_tracker dsr_tracker;
 enum {
   DSR_TRACK_OK = 0,
@@ -905,17 +908,19 @@ typedef struct {
   int status;                     /* DSR_TRACK_* */
   int n_pts;                      /* points the GN started with */
   int n_inliers;                  /* points the filter kept; n_pts when it does not run (optimizer.py:77) */
-  int n_near, n_crop;             /* a sweep call: the ingest's counts (dsr_lidar_det_out); host rows: 0 */
+  int n_near, n_crop;             /* the ingest's counts.  A sweep call: n_near, n_crop of dsr_lidar_det_out;
+                                     a frame call: n_mask, n_valid of dsr_frame_det_out; host rows: 0 */
 } dsr_track_out;
 typedef struct {
   float scale;                    /* the map object's scale (pMO->scale, LocalMapping_util.cc:110) */
-  int pose_given;                 /* != 0: t_co_se3 is the start pose (e.g. Tcw Two of :106) */
+  int pose_given;                 /* != 0: t_co_se3 is the start pose (e.g. Tcw Two of :106); a frame call needs it */
   float t_co_se3[16];             /* SE(3) camera<-object; read only with pose_given */
 } dsr_track_det;
 /* A tracker of at most max_obj objects x max_pts points per call, for the decoder and the
- * pose-only settings of p (pose_only_iterations, code_len; optimizer.py:46-87).  Nothing but the
- * sweep block of dsr_tracker_track_lidar (it grows with the largest sweep seen) is allocated
- * after this call.  Errors: a null argument, max_obj < 1, max_pts outside 1 .. 2^20, max_obj x
+ * pose-only settings of p (pose_only_iterations, code_len; optimizer.py:46-87).  Nothing but two
+ * ingest blocks is allocated after this call: the sweep block of dsr_tracker_track_lidar, which
+ * grows with the largest sweep seen, and the image block of dsr_tracker_track_frame, which grows
+ * with the largest image seen.  Errors: a null argument, max_obj < 1, max_pts outside 1 .. 2^20, max_obj x
  * max_pts above 2^22, a code_len mismatch. */
 int dsr_tracker_create(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_params* p, int max_obj,
                        int max_pts, dsr_tracker** out);
@@ -940,6 +945,26 @@ int dsr_tracker_track(dsr_tracker* tr, int n_obj, const dsr_pose_in* in);
 int dsr_tracker_track_lidar(dsr_tracker* tr, const dsr_lidar_params* params, const float* t_cam_velo,
                             const float* velo, int n_velo, int stride, int n_det, const dsr_lidar_det* dets,
                             const dsr_track_det* prior);
+/* The same from a depth image and an instance-label image (the RGB-D path, which has no sweep):
+ * detection i's points are exactly the surface-point rows DESIGN.md 3.5b gives it — the pixels
+ * with instance == label and near < z < far in row-major order, n_pts = min(n_valid, max_pts), row
+ * k from valid pixel sel(k, max_pts, n_valid) as (rx z, ry z, z) — written by the ingest's kernels
+ * into the tracker's point block.  No ray, observed depth, background grid or box is written and
+ * no background pass runs.  Of params only max_pts (<= the tracker's), min_mask_area, near and far
+ * are read; of dets[i] only label and code, the map object's code (not NULL).  prior[i] carries
+ * the map object's scale and the start pose: pose_given must be non-zero (there is no 3-D
+ * detector on this path; the caller passes Tcw Two, LocalMapping_util.cc:106).  A detection whose
+ * ingest status is not DSR_FRAME_OK (no mask, a mask of at most min_mask_area pixels, no valid
+ * depth) has n_pts = 0: DSR_TRACK_NO_POINTS and a NaN pose.  Two detections may carry the same
+ * label.  The record's n_near, n_crop hold the ingest's n_mask, n_valid.  Ordering as
+ * dsr_tracker_track_lidar: the images and the detections go through a pinned block of the handle
+ * in one upload on the context stream.  Errors, returned before the device is touched (the handle
+ * stays usable): a null argument, n_det outside 1 .. max_obj, max_pts above the tracker's, those
+ * of dsr_frame_inputs_host for the fields that are read (image size, focal lengths, max_pts < 1),
+ * a null code, pose_given == 0, a scale that is not positive and finite, a non-finite pose. */
+int dsr_tracker_track_frame(dsr_tracker* tr, const dsr_camera* cam, const dsr_frame_params* params,
+                            const float* depth, const int* instance, int n_det,
+                            const dsr_frame_det* dets, const dsr_track_det* prior);
 /* 1: the last call has finished, 0: still in flight (as dsr_batch_query), < 0: an error. */
 int dsr_tracker_query(dsr_tracker* tr);
 /* Waits for the last call and writes its poses (t_out: n x 16, the rotation block divided by the

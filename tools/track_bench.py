@@ -1,6 +1,7 @@
 """The resident object tracker (dsr_tracker_*) against the one-shot pose-only entry
 points on the same build and machine: N tracked objects x 250 points (num_lidar_max) at 5 and 7
-pose-only iterations, N = 8 and 32, and one 120 k-point sweep with 8 detections.
+pose-only iterations, N = 8 and 32, one 120 k-point sweep with 8 detections, and one 640 x 480
+rendered frame of 8 objects.
 
   loop:     Optimizer.estimate_pose_cam_obj once per object (the reference's call pattern,
             LocalMapping_util.cc:103-110)
@@ -10,6 +11,11 @@ pose-only iterations, N = 8 and 32, and one 120 k-point sweep with 8 detections.
   sweep:    the ingest rows on the device, then the batch (dsr_lidar_inputs, then
             estimate_pose_cam_obj_batch on the rows it copies back) against
             Optimizer.track_lidar_frame
+  frame:    a depth image + instance image at 7 iterations, max_pts = 250.  rows_then_track: the
+            rows on the host (utils.frame_inputs: a W x H scan per detection), then the resident
+            tracker's track() from those rows — what a caller does without the new entry point;
+            track_frame: ObjectTracker.track_frame (the rows are built on the device).  call_ms
+            until the call returns, done_ms until result() returns the poses.
 
 Host clock; every "done" figure ends in a stream synchronise (the blocking entry points and
 result() all do).  All legs are warmed up, then timed in alternation; medians of --reps rounds with
@@ -17,6 +23,7 @@ min and max.  The tracker's poses are compared bitwise with the batch's first an
 reported.  No pass/fail threshold.
 
 Usage (GPU box): python tools/track_bench.py [--reps 15] [--out profiles/track_bench.json]
+                 python tools/track_bench.py --legs frame --frame-out profiles/track_frame.json
 """
 import argparse
 import json
@@ -32,7 +39,10 @@ ap.add_argument("--reps", type=int, default=15)
 ap.add_argument("--out", default=None)
 ap.add_argument("--points", type=int, default=250)
 ap.add_argument("--sweep-points", type=int, default=120000)
+ap.add_argument("--legs", default="rows,sweep,frame", help="comma-separated: rows, sweep, frame")
+ap.add_argument("--frame-out", default=None, help="the frame leg's JSON (profiles/track_frame.json)")
 a = ap.parse_args()
+LEGS = set(a.legs.split(","))
 
 REPO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, os.path.abspath(os.path.join(REPO, "dsp-slam-rgbd_amd")))
@@ -40,7 +50,7 @@ import synthetic as S  # noqa: E402
 from deep_sdf.workspace import decoder_from_state  # noqa: E402
 from reconstruct import _libdsr as L  # noqa: E402
 from reconstruct import utils as U  # noqa: E402
-from reconstruct.optimizer import Optimizer  # noqa: E402
+from reconstruct.optimizer import Optimizer, SdfRenderer  # noqa: E402
 
 dec = decoder_from_state(S.make_decoder(1234), S.DEFAULT_SPECS)
 
@@ -83,7 +93,7 @@ def timed(legs, reps):
 
 
 res = {"tool": "tools/track_bench.py", "points": a.points, "reps": a.reps, "rows": []}
-for iters in (5, 7):
+for iters in (5, 7) if "rows" in LEGS else ():
     opt = optimizer(iters)
     for n in (8, 32):
         obs = objects(n)
@@ -147,7 +157,7 @@ velo_c, inst_c, tcv16 = U.lidar_sweep(velo, inst, lcam, tcv)
 ldets, keep_d = U.lidar_dets(dets)
 lmasks = U.lidar_masks([])
 sweep_rows = []
-for iters in (5, 7):
+for iters in (5, 7) if "sweep" in LEGS else ():
     opt = optimizer(iters)
     ctx = opt._ctx
     pts = np.zeros((N, a.points, 3), np.float32)
@@ -182,6 +192,72 @@ for iters in (5, 7):
     print(json.dumps({k: (v if not isinstance(v, dict) else {q: round(x["median"], 4) for q, x in v.items()})
                       for k, v in row.items() if k not in ("n_pts", "n_crop")}), flush=True)
 res["sweep"] = sweep_rows
+
+
+# ---- the frame leg: 8 rendered objects at 640 x 480
+def frame_leg():
+    FW, FH, iters = 640, 480, 7
+    fcam = dict(width=FW, height=FH, fx=525.0, fy=525.0, cx=319.5, cy=239.5)
+    fparams = dict(max_pts=a.points)
+    codes = [(0.02 * np.random.default_rng(100 + i).standard_normal(64)).astype(np.float32) for i in range(N)]
+    sim3, starts, scales = [], [], []
+    for i in range(N):
+        T = S.make_object(7 + i, n_pts=8, scale=2.0, tz=12, perturb=0).t_true.astype(np.float32)
+        T[:3, 3] = ((-4.5, -1.5, 1.5, 4.5)[i % 4], (-1.6, 1.6)[i // 4], 12.0 + 0.25 * i)
+        sc = float(np.cbrt(np.linalg.det(T[:3, :3].astype(np.float64))))
+        T0 = T.copy()
+        T0[:3, :3] /= np.float32(sc)
+        T0[:3, 3] += np.float32(0.05)
+        sim3.append(T)
+        starts.append(T0)
+        scales.append(sc)
+    ren = SdfRenderer(dec, FW, FH, fcam["fx"], fcam["fy"], fcam["cx"], fcam["cy"])
+    img = ren.render([(sim3[i], codes[i]) for i in range(N)])
+    ren.close()
+    depth, inst = img["depth"], img["instance"]
+    opt = optimizer(iters)
+    tr = opt._tracker_for(N, a.points)
+    host_dets = [dict(label=i, t_cam_obj=starts[i]) for i in range(N)]
+    fdets = [dict(label=i, code=codes[i]) for i in range(N)]
+    priors = [(scales[i], starts[i]) for i in range(N)]
+    got = {}
+
+    def rows_then_track():
+        t0 = time.perf_counter()
+        objs, _ = U.frame_inputs(depth, inst, host_dets, fcam, **fparams)
+        t1 = time.perf_counter()
+        tr.track([(starts[i], scales[i], objs[i][1], codes[i]) for i in range(N)])
+        t2 = time.perf_counter()
+        got["rows"] = tr.result()
+        return {"rows_ms": 1e3 * (t1 - t0), "call_ms": 1e3 * (t2 - t0), "done_ms": 1e3 * (time.perf_counter() - t0)}
+
+    def track_frame():
+        t0 = time.perf_counter()
+        tr.track_frame(depth, inst, fdets, priors, fcam, fparams)
+        t1 = time.perf_counter()
+        got["frame"] = tr.result()
+        return {"call_ms": 1e3 * (t1 - t0), "done_ms": 1e3 * (time.perf_counter() - t0)}
+
+    rows_then_track()
+    track_frame()
+    recs = got["frame"][1]
+    row = {"objects": N, "iterations": iters, "width": FW, "height": FH, "max_pts": a.points,
+           "identical_poses": bool(np.array_equal(bits(got["frame"][0]), bits(got["rows"][0]))),
+           "n_pts": [int(r.n_pts) for r in recs], "n_valid": [int(r.n_crop) for r in recs],
+           "n_inliers": [int(r.n_inliers) for r in recs]}
+    row.update(timed({"rows_then_track": rows_then_track, "track_frame": track_frame}, a.reps))
+    print(json.dumps({k: (v if not isinstance(v, dict) else {q: round(x["median"], 4) for q, x in v.items()})
+                      for k, v in row.items() if k not in ("n_pts", "n_valid", "n_inliers")}), flush=True)
+    return row
+
+
+if "frame" in LEGS:
+    res["frame"] = frame_leg()
+    if a.frame_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.frame_out)), exist_ok=True)
+        with open(a.frame_out, "w") as fo:
+            json.dump({"tool": "tools/track_bench.py --legs frame", "reps": a.reps, "frame": res["frame"]}, fo, indent=1)
+            fo.write("\n")
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fo:
