@@ -27,6 +27,7 @@
 #include "dsr_render.hpp"
 #include "dsr_scene.hpp"
 #include "dsr_frame.hpp"
+#include "dsr_assoc.hpp"
 #include "dsr_lidar.hpp"
 #include "dsr_track.hpp"
 
@@ -3834,6 +3835,11 @@ struct dsr_scene {
   int held0 = 0, held_k = 0;         // the objects whose candidates the pass buffers hold
   std::vector<int> q_in;             // the last query's n_in
   dsr_scene_stats st{};
+  // association (dsr_scene_associate_*, §3.6d): allocated at the first call that needs them
+  float* arows = nullptr;            // camera-frame rows, max_pts x 3
+  dsr_batch::IngestBlock aframe;     // a frame call's block (frame_carve): it grows
+  dsr_batch::IngestBlock ablock;     // counts, descriptors, rows, tables and records (assoc_layout): it grows
+  hipEvent_t a_ev = nullptr;         // recorded after a call's last copy
 };
 
 // One object's pose for the query: T_ow = inverse(t_world_obj) in fp64 (adjugate / determinant, as
@@ -3892,6 +3898,11 @@ int dsr_scene_destroy(dsr_scene* sc) {
   hipStreamSynchronize(sc->ctx->stream);
   for (hipEvent_t e : sc->ev)
     if (e) hipEventDestroy(e);
+  if (sc->a_ev) hipEventDestroy(sc->a_ev);
+  for (dsr_batch::IngestBlock* g : {&sc->aframe, &sc->ablock}) {
+    if (g->host) hipHostFree(g->host);
+    if (g->dev) hipFree(g->dev);
+  }
   delete sc;
   return 0;
 }
@@ -4155,6 +4166,258 @@ int dsr_scene_peek(dsr_scene* sc, int obj, int cap, int* idx, float* x_obj, floa
     if (sdf) sdf[j] = hd[i];
   }
   return 0;
+}
+
+// ---- data association (kernels and the shared rule: dsr_assoc.hpp) ----------
+int dsr_assoc_params_default(dsr_assoc_params* p) {
+  if (!p) return -2;
+  p->inlier_tol = 0.05f;
+  p->min_hits = 20;
+  p->min_pct = 50;
+  return 0;
+}
+
+// what an association reads of the frame parameters (as dsr_tracker_track_frame: no background
+// grid, the mask's tight box) and its detections, one per label
+static dsr_frame_params assoc_frame_params(const dsr_frame_params* P) {
+  return dsr_frame_params{P->max_pts, 0, 1, 0, P->min_mask_area, P->near, P->far};
+}
+static std::vector<dsr_frame_det> assoc_frame_dets(int n_det, const int* labels) {
+  std::vector<dsr_frame_det> dets(n_det > 0 ? n_det : 0);
+  for (int j = 0; j < n_det; ++j) {
+    dets[j] = dsr_frame_det{};
+    dets[j].label = labels[j];
+    dets[j].bbox[2] = dets[j].bbox[3] = -1;
+  }
+  return dets;
+}
+static bool assoc_rigid(const float* t) {
+  float inv[16];
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(t[i])) return false;
+  return rigid_inverse(t, inv);
+}
+
+int dsr_assoc_points_host(const dsr_camera* cam, const dsr_frame_params* frame_params, const float* t_world_cam,
+                          const float* depth, const int* instance, int n_det, const int* labels,
+                          float* pts_world, int* n_rows, dsr_frame_det_out* ingest) {
+  if (!frame_params || !t_world_cam || !labels || !pts_world || !n_rows || n_det < 1) return -2;
+  const dsr_frame_params Q = assoc_frame_params(frame_params);
+  const std::vector<dsr_frame_det> dets = assoc_frame_dets(n_det, labels);
+  if (frame_args_error(cam, &Q, depth, instance, n_det, dets.data())) return -2;
+  if (!assoc_rigid(t_world_cam)) return -2;
+  const size_t slots = (size_t)n_det * Q.max_pts;
+  std::vector<float> rows(slots * 3, 0.f);
+  std::vector<dsr_frame_det_out> recs(n_det);
+  frame_inputs_host_impl(frame_cam(cam), Q, depth, instance, n_det, dets.data(), rows.data(), nullptr, nullptr, recs.data());
+  const AssocXf X = assoc_xf(t_world_cam);
+  for (int j = 0; j < n_det; ++j) {
+    n_rows[j] = recs[j].n_pts;
+    if (ingest) ingest[j] = recs[j];
+    for (int k = 0; k < Q.max_pts; ++k) {
+      const size_t p = (size_t)j * Q.max_pts + k;
+      float* w = pts_world + p * 3;
+      if (k < recs[j].n_pts) assoc_world(X, &rows[p * 3], w);
+      else w[0] = w[1] = w[2] = __builtin_nanf("");
+    }
+  }
+  return 0;
+}
+
+int dsr_assoc_pick_host(const dsr_assoc_params* assoc_params, int n_det, int n_obj, const int* table,
+                        const int* n_rows, dsr_assoc_out* out) {
+  if (assoc_params_error(assoc_params) || n_det < 1 || n_obj < 0 || (n_obj > 0 && !table) || !n_rows || !out) return -2;
+  for (int j = 0; j < n_det; ++j)
+    if (n_rows[j] < 0) return -2;
+  const size_t plane = (size_t)n_det * n_obj;
+  for (int j = 0; j < n_det; ++j) {
+    const int* row = n_obj ? table + (size_t)j * n_obj : nullptr;
+    assoc_pick_host_one(*assoc_params, n_obj, row, n_obj ? row + plane : nullptr, n_obj ? row + 2 * plane : nullptr,
+                        n_rows[j], out + j);
+  }
+  return 0;
+}
+
+namespace {
+struct AssocFrame {                  // a frame call's source: the images, through sc->aframe
+  const dsr_camera* cam;
+  dsr_frame_params Q;
+  const float* depth;
+  const int* inst;
+  const std::vector<dsr_frame_det>* dets;
+};
+}  // namespace
+
+// Everything of a call after its refusals.  F != null: the rows are the frame ingest's; else the
+// caller's (rows, n_rows).  Every copy and kernel is enqueued on the context stream; the one wait
+// of the host is at the end.  (The caller, assoc_run, holds the run lock and drains the stream if
+// this returns an error.)
+static int assoc_enqueue_wait(dsr_scene* sc, const dsr_assoc_params& A, const float* t_world_cam, int n_det,
+                              int max_pts, const AssocFrame* F, const int* n_rows, const float* rows,
+                              dsr_assoc_out* out, int* table) {
+  dsr_ctx* ctx = sc->ctx;
+  hipStream_t s = ctx->stream;
+  const int n_obj = sc->n_obj, n_pts = n_det * max_pts;
+  sc->q_obj = -1;
+  sc->held_k = 0;
+  if (!sc->a_ev) DSR_CHECK(ctx, hipEventCreateWithFlags(&sc->a_ev, hipEventDisableTiming));
+  if (!sc->arows && !sc->mem.alloc(&sc->arows, 3 * (size_t)sc->max_pts)) {
+    sc->arows = nullptr;
+    return fail(ctx, "hipMalloc failed (scene association)");
+  }
+  // ---- staging: counts, descriptors and host rows into the pinned half, the frame into its block
+  size_t row_floats = 0;
+  if (!F)
+    for (int j = n_det - 1; j >= 0 && !row_floats; --j)
+      if (n_rows[j] > 0) row_floats = ((size_t)j * max_pts + n_rows[j]) * 3;      // up to the last counted row
+  const AssocLayout L = assoc_layout(n_det, n_obj, row_floats);
+  if (int rc = ingest_fit(ctx, sc->ablock, sc->a_ev, L.host_bytes, L.dev_bytes)) return rc;
+  char* hb = static_cast<char*>(sc->ablock.host);
+  char* db = static_cast<char*>(sc->ablock.dev);
+  int* d_cnt = reinterpret_cast<int*>(db + L.d_cnt);
+  int* d_table = reinterpret_cast<int*>(db + L.d_table);
+  dsr_assoc_out* d_recs = reinterpret_cast<dsr_assoc_out*>(db + L.d_recs);
+  // passes as dsr_scene_query's: objects in input order, the largest k <= 64 with k * n_pts pairs
+  const size_t pass_obj = hook_int("DSR_SCENE_PASS_OBJ", SCENE_PASS_OBJ, 1, SCENE_PASS_OBJ);
+  const int k_pass = (int)std::min(pass_obj, sc->cap / (size_t)n_pts);
+  ObjDesc* hdesc = reinterpret_cast<ObjDesc*>(hb + L.desc);
+  for (int i = 0; i < n_obj; ++i) {
+    sc->hdesc[i] = ObjDesc{};
+    sc->hdesc[i].cand_off = (i % k_pass) * n_pts;
+    hdesc[i] = sc->hdesc[i];
+  }
+  int* hcnt = reinterpret_cast<int*>(hb + L.cnt);
+  for (int j = 0; j < n_det; ++j) hcnt[j] = F ? 0 : n_rows[j];
+  const dsr_frame_det_out* d_frecs = nullptr;
+  FrameDev FD{};
+  size_t fup = 0;
+  if (F) {
+    const int W = F->cam->width, H = F->cam->height;
+    fup = frame_upload_bytes(W, H, n_det);
+    if (int rc = ingest_fit(ctx, sc->aframe, sc->a_ev, fup, frame_dev_bytes(W, H, n_det))) return rc;
+    frame_pack(sc->aframe.host, F->cam, F->depth, F->inst, n_det, F->dets->data());
+    FD = frame_carve(sc->aframe.dev, W, H, n_det);
+    d_frecs = FD.recs;
+  } else {
+    float* hrows = reinterpret_cast<float*>(hb + L.rows);
+    for (int j = 0; j < n_det; ++j)
+      if (n_rows[j] > 0)
+        std::memcpy(hrows + (size_t)j * max_pts * 3, rows + (size_t)j * max_pts * 3, sizeof(float) * 3 * n_rows[j]);
+  }
+  // ---- uploads
+  DSR_CHECK(ctx, hipMemcpyAsync(d_cnt, hcnt, sizeof(int) * n_det, hipMemcpyHostToDevice, s));
+  if (n_obj > 0) DSR_CHECK(ctx, hipMemcpyAsync(sc->desc, hdesc, sizeof(ObjDesc) * n_obj, hipMemcpyHostToDevice, s));
+  if (row_floats)
+    DSR_CHECK(ctx, hipMemcpyAsync(sc->arows, hb + L.rows, sizeof(float) * row_floats, hipMemcpyHostToDevice, s));
+  if (F) DSR_CHECK(ctx, hipMemcpyAsync(sc->aframe.dev, sc->aframe.host, fup, hipMemcpyHostToDevice, s));
+  if (n_obj > 0) DSR_CHECK(ctx, hipMemsetAsync(d_table, 0, sizeof(int) * 3 * (size_t)n_det * n_obj, s));
+  // ---- the rows (a frame call: the ingest's row passes and the points-only emit, at the fixed
+  // stride max_pts), then the world points
+  if (F) {
+    const FrameCam FC = frame_cam(F->cam);
+    const unsigned gy = (unsigned)((FC.H + FRAME_WAVES - 1) / FRAME_WAVES);
+    hipLaunchKernelGGL(k_frame_rows, dim3(gy, n_det), dim3(FRAME_WG), 0, s, FC, F->Q, (const float*)FD.depth,
+                       (const int*)FD.inst, (const FrameDet*)FD.dets, FD.rows);
+    hipLaunchKernelGGL(k_frame_scan, dim3(n_det), dim3(FRAME_WG), 0, s, FC, F->Q, (const int*)FD.inst,
+                       (const FrameDet*)FD.dets, (const int4*)FD.rows, FD.voff, FD.bgoff, FD.aux, FD.recs, (ObjDesc*)nullptr);
+    hipLaunchKernelGGL(k_frame_emit<false>, dim3(gy, n_det), dim3(FRAME_WG), 0, s, FC, F->Q, (const float*)FD.depth,
+                       (const int*)FD.inst, (const FrameDet*)FD.dets, (const int4*)FD.rows, (const int*)FD.voff,
+                       (const int*)FD.bgoff, (const int*)FD.aux, (const dsr_frame_det_out*)FD.recs,
+                       (const ObjDesc*)nullptr, sc->arows, (float*)nullptr, (float*)nullptr);
+  }
+  hipLaunchKernelGGL(k_assoc_world, dim3((n_pts + ASSOC_WG - 1) / ASSOC_WG), dim3(ASSOC_WG), 0, s, n_pts, max_pts,
+                     assoc_xf(t_world_cam), (const float*)sc->arows, (const int*)d_cnt, d_frecs, sc->pts);
+  // ---- the value passes, back to back: the tile count stays on the device
+  dsr_scene_stats st{};
+  st.n_obj = n_obj;
+  st.n_pts = n_pts;
+  st.pairs = (long long)n_obj * n_pts;
+  const int grid = std::max(1, std::min(ctx->n_cu, k_pass * ((n_pts + TILE - 1) / TILE)));
+  for (int o0 = 0; o0 < n_obj; o0 += k_pass) {
+    const int k = std::min(k_pass, n_obj - o0);
+    st.n_passes += 1;
+    if (int rc = scene_value_pass(sc, o0, k, n_pts, false, false)) return rc;
+    hipLaunchKernelGGL(k_assoc_vote, dim3(grid), dim3(TILE), 0, s, (const ObjDesc*)sc->desc, (const Tile*)sc->tiles,
+                       (const int*)sc->ntiles, (const float4*)sc->cand, (const float*)sc->dense, max_pts, n_det, n_obj,
+                       A.inlier_tol, d_table);
+  }
+  hipLaunchKernelGGL(k_assoc_pick, dim3(n_det), dim3(64), 0, s, A, n_det, n_obj, (const int*)d_table, (const int*)d_cnt,
+                     d_frecs, d_recs);
+  DSR_CHECK(ctx, hipGetLastError());
+  // ---- the tables, the records and the objects' candidate counts come back; the call's one wait
+  const size_t tb = sizeof(int) * 3 * (size_t)n_det * n_obj;
+  if (n_obj > 0) DSR_CHECK(ctx, hipMemcpyAsync(hb + L.table, d_table, tb, hipMemcpyDeviceToHost, s));
+  DSR_CHECK(ctx, hipMemcpyAsync(hb + L.recs, d_recs, sizeof(dsr_assoc_out) * n_det, hipMemcpyDeviceToHost, s));
+  if (n_obj > 0) DSR_CHECK(ctx, hipMemcpyAsync(hb + L.desc, sc->ocount, sizeof(int) * n_obj, hipMemcpyDeviceToHost, s));
+  DSR_CHECK(ctx, hipEventRecord(sc->a_ev, s));
+  DSR_CHECK(ctx, hipStreamSynchronize(s));
+  std::memcpy(out, hb + L.recs, sizeof(dsr_assoc_out) * n_det);
+  if (table && n_obj > 0) std::memcpy(table, hb + L.table, tb);
+  sc->q_in.assign(n_obj, 0);
+  if (n_obj > 0) std::memcpy(sc->q_in.data(), hb + L.desc, sizeof(int) * n_obj);
+  for (int i = 0; i < n_obj; ++i) st.decoded += sc->q_in[i];
+  sc->st = st;
+  sc->q_obj = n_obj;                 // dsr_scene_peek speaks of this call's points
+  sc->q_pts = n_pts;
+  return 0;
+}
+
+// A HIP error in the middle of a call must not leave a copy out of (or into) the pinned blocks in
+// flight: the stream is drained before the error is returned, so the next call's staging is free,
+// as after dsr_scene_query's blocking copies.
+static int assoc_run(dsr_scene* sc, const dsr_assoc_params& A, const float* t_world_cam, int n_det, int max_pts,
+                     const AssocFrame* F, const int* n_rows, const float* rows, dsr_assoc_out* out, int* table) {
+  dsr_ctx* ctx = sc->ctx;
+  if (int rc = decoder_ready(ctx, sc->dec)) return rc;
+  std::lock_guard<std::recursive_mutex> run(ctx->run_mu);
+  hipSetDevice(ctx->device);
+  const int rc = assoc_enqueue_wait(sc, A, t_world_cam, n_det, max_pts, F, n_rows, rows, out, table);
+  if (rc != 0) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+// the refusals both forms share, after their own null checks
+static const char* assoc_args_error(const dsr_scene* sc, const dsr_assoc_params* A, const float* t_world_cam, int n_det,
+                                    int max_pts) {
+  if (sc->n_obj < 0) return "dsr_scene_associate before dsr_scene_set_objects";
+  if (n_det < 1) return "associate: n_det must be >= 1";
+  if (max_pts < 1) return "associate: max_pts must be >= 1";
+  if ((long long)n_det * max_pts > sc->max_pts) return "associate: n_det x max_pts exceeds the scene's max_pts";
+  if (t_world_cam && !assoc_rigid(t_world_cam))
+    return "associate: t_world_cam is not rigid (finite, last row 0 0 0 1, R^T R = I within 1e-4, det R > 0)";
+  return assoc_params_error(A);
+}
+
+int dsr_scene_associate_frame(dsr_scene* sc, const dsr_camera* cam, const dsr_frame_params* frame_params,
+                              const dsr_assoc_params* assoc_params, const float* t_world_cam,
+                              const float* depth, const int* instance, int n_det, const int* labels,
+                              dsr_assoc_out* out, int* table) {
+  if (!sc) return -2;
+  dsr_ctx* ctx = sc->ctx;
+  if (!cam || !frame_params || !assoc_params || !t_world_cam || !depth || !instance || !labels || !out)
+    return fail(ctx, "null argument");
+  if (n_det < 1) return fail(ctx, "associate: n_det must be >= 1");
+  AssocFrame F{cam, assoc_frame_params(frame_params), depth, instance, nullptr};
+  const std::vector<dsr_frame_det> dets = assoc_frame_dets(n_det, labels);
+  F.dets = &dets;
+  if (const char* m = frame_args_error(cam, &F.Q, depth, instance, n_det, dets.data())) return fail(ctx, m);
+  if (const char* m = assoc_args_error(sc, assoc_params, t_world_cam, n_det, F.Q.max_pts)) return fail(ctx, m);
+  return assoc_run(sc, *assoc_params, t_world_cam, n_det, F.Q.max_pts, &F, nullptr, nullptr, out, table);
+}
+
+int dsr_scene_associate_points(dsr_scene* sc, const dsr_assoc_params* assoc_params, const float* t_world_cam,
+                               int n_det, int max_pts, const int* n_rows, const float* rows,
+                               dsr_assoc_out* out, int* table) {
+  if (!sc) return -2;
+  dsr_ctx* ctx = sc->ctx;
+  if (!assoc_params || !n_rows || !rows || !out) return fail(ctx, "null argument");
+  if (const char* m = assoc_args_error(sc, assoc_params, t_world_cam, n_det, max_pts)) return fail(ctx, m);
+  for (int j = 0; j < n_det; ++j)
+    if (n_rows[j] < 0 || n_rows[j] > max_pts) return fail(ctx, "associate: n_rows must be in [0, max_pts]");
+  return assoc_run(sc, *assoc_params, t_world_cam, n_det, max_pts, nullptr, n_rows, rows, out, table);
 }
 
 // ------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
  *   dsr_c_stress               no-device paths: ABI version, argument validation and error
  *                              reporting of every entry point that checks its arguments before
  *                              touching the device, the host rules (dsr_scene_bin_host,
+ *                              dsr_assoc_pick_host, dsr_assoc_points_host,
  *                              dsr_lidar_inputs_host, dsr_lidar_track_prep_host) on hand-computed
  *                              inputs, context creation
  *                              (-3 without a device)
@@ -19,7 +20,9 @@
  *                              mesher (and dsr_mc_volume on its decoded grid) with ample and
  *                              with too small capacities, the batch call (dsr_mesher_run_batch:
  *                              ample and too small totals, n = 0) against it, scene queries
- *                              (dsr_scene_*) against sdf_eval and their records, the LiDAR
+ *                              (dsr_scene_*) against sdf_eval and their records, data association
+ *                              (dsr_scene_associate_* against a recount over dsr_scene_peek and
+ *                              the frame form against the points form), the LiDAR
  *                              ingest (dsr_lidar_inputs against a hand-computed sweep and the
  *                              host rule, dsr_batch_refill_lidar against dsr_batch_refill), the
  *                              resident tracker (dsr_tracker_* from the same sweep, from host
@@ -403,6 +406,65 @@ static void no_device_paths(void) {
     CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(reflection) accepted");
     so[1].t_world_obj[0] = inf;
     CHECK(dsr_scene_bin_host(2, so, 7, pw, 0, 7, idx, xo, &n_in, &scale) < 0, "scene_bin_host(inf pose) accepted");
+  }
+  {
+    /* data association: null arguments, the defaults, the host pick on a hand-made table (a tie,
+       min_pct at equality, no points) and the host points of a 4 x 3 image under a translation */
+    dsr_assoc_params ap;
+    CHECK(dsr_assoc_params_default(NULL) < 0, "assoc_params_default(NULL) accepted");
+    CHECK(dsr_assoc_params_default(&ap) == 0 && ap.inlier_tol == 0.05f && ap.min_hits == 20 && ap.min_pct == 50,
+          "assoc defaults");
+    dsr_assoc_out ao[3];
+    int nr[3] = {40, 60, 0};
+    const float eye[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+    CHECK(dsr_scene_associate_points(NULL, &ap, eye, 3, 4, nr, eye, ao, NULL) < 0, "associate_points(NULL) accepted");
+    CHECK(dsr_scene_associate_frame(NULL, NULL, NULL, &ap, eye, NULL, NULL, 1, nr, ao, NULL) < 0,
+          "associate_frame(NULL) accepted");
+    /*                     n_in               n_hit              n_neg */
+    const int tab[27] = {30, 30, 5,  50, 9, 9,  0, 0, 0,     25, 25, 0,  30, 7, 7,  0, 0, 0,     1, 2, 3,  4, 5, 6,  0, 0, 0};
+    CHECK(dsr_assoc_pick_host(&ap, 3, 3, tab, nr, ao) == 0, "assoc_pick_host failed");
+    CHECK(ao[0].status == DSR_ASSOC_MATCHED && ao[0].obj == 0 && ao[0].second == 1 && ao[0].second_hit == 25 &&
+          ao[0].n_in == 30 && ao[0].n_neg == 1, "pick: a tie goes to the lower index (%d %d)", ao[0].obj, ao[0].second);
+    CHECK(ao[1].status == DSR_ASSOC_NEW && ao[1].obj == -1 && ao[1].n_hit == 30 && ao[1].second == 1 && ao[1].second_hit == 7,
+          "pick: 100 * 30 == 50 * 60 is not a majority (%d)", ao[1].status);
+    CHECK(ao[2].status == DSR_ASSOC_NO_POINTS && ao[2].obj == -1 && ao[2].n_pts == 0, "pick: no points (%d)", ao[2].status);
+    CHECK(dsr_assoc_pick_host(&ap, 3, 0, NULL, nr, ao) == 0 && ao[0].status == DSR_ASSOC_NEW && ao[0].second == -1,
+          "pick: an empty map");
+    CHECK(dsr_assoc_pick_host(NULL, 3, 3, tab, nr, ao) < 0 && dsr_assoc_pick_host(&ap, 0, 3, tab, nr, ao) < 0 &&
+          dsr_assoc_pick_host(&ap, 3, 3, NULL, nr, ao) < 0 && dsr_assoc_pick_host(&ap, 3, 3, tab, NULL, ao) < 0 &&
+          dsr_assoc_pick_host(&ap, 3, 3, tab, nr, NULL) < 0, "assoc_pick_host(bad argument) accepted");
+    dsr_assoc_params bad = ap;
+    bad.inlier_tol = 0.f;
+    CHECK(dsr_assoc_pick_host(&bad, 3, 3, tab, nr, ao) < 0, "inlier_tol 0 accepted");
+    bad = ap; bad.min_hits = 0;
+    CHECK(dsr_assoc_pick_host(&bad, 3, 3, tab, nr, ao) < 0, "min_hits 0 accepted");
+    bad = ap; bad.min_pct = 100;
+    CHECK(dsr_assoc_pick_host(&bad, 3, 3, tab, nr, ao) < 0, "min_pct 100 accepted");
+    dsr_camera cam = {4, 3, 2.f, 2.f, 1.f, 1.f};
+    dsr_frame_params fp;
+    dsr_frame_params_default(&fp);
+    fp.max_pts = 3; fp.min_mask_area = 1;
+    const float depth[12] = {2.f, 2.f, 0.f, 2.f,   4.f, 2.f, 2.f, 2.f,   2.f, 2.f, 2.f, 8.f};
+    const int inst[12] = {5, 5, 5, 0,   5, 0, 0, 0,   0, 0, 0, 5};
+    const int labels[2] = {5, 9};
+    float tw[16];
+    memcpy(tw, eye, sizeof tw);
+    tw[3] = 10.f; tw[7] = 20.f; tw[11] = 30.f;
+    float pw[2 * 3 * 3];
+    int rows[2] = {-1, -1};
+    dsr_frame_det_out fo[2];
+    CHECK(dsr_assoc_points_host(&cam, &fp, tw, depth, inst, 2, labels, pw, rows, fo) == 0, "assoc_points_host failed");
+    /* valid pixels of label 5: (0,0) (1,0) (0,1) (3,2), three of four kept by sel: 0, 1, 3 */
+    CHECK(rows[0] == 3 && rows[1] == 0 && fo[0].n_mask == 5 && fo[0].n_valid == 4 && fo[1].status == DSR_FRAME_NO_MASK,
+          "assoc_points_host counts %d %d", rows[0], rows[1]);
+    CHECK(pw[0] == 9.f && pw[1] == 19.f && pw[2] == 32.f && pw[3] == 10.f && pw[6] == 18.f && pw[7] == 24.f && pw[8] == 38.f,
+          "assoc_points_host rows %g %g %g", pw[0], pw[6], pw[8]);
+    for (int k = 9; k < 18; ++k) CHECK(pw[k] != pw[k], "assoc_points_host: NaN fill %d", k);
+    CHECK(dsr_assoc_points_host(&cam, &fp, NULL, depth, inst, 2, labels, pw, rows, fo) < 0 &&
+          dsr_assoc_points_host(&cam, &fp, tw, depth, inst, 0, labels, pw, rows, fo) < 0 &&
+          dsr_assoc_points_host(NULL, &fp, tw, depth, inst, 2, labels, pw, rows, fo) < 0, "assoc_points_host(bad argument) accepted");
+    tw[0] = -1.f;
+    CHECK(dsr_assoc_points_host(&cam, &fp, tw, depth, inst, 2, labels, pw, rows, fo) < 0, "a reflected t_world_cam accepted");
   }
   lidar_no_device_paths();
   dsr_ctx* c = NULL;
@@ -1004,6 +1066,87 @@ int main(int argc, char** argv) {
     CHECK(dsr_scene_stats_get(sc, &sst) == 0 && sst.n_obj == 2 && sst.n_pts == n && sst.n_passes == 1 &&
           sst.pairs == 2 * n && sst.decoded == rec[0].n_in + rec[1].n_in && sst.winners == n, "scene stats");
     CHECK(dsr_scene_query(sc, 0, NULL, NULL, NULL, NULL, rec) == 0 && rec[0].n_in == 0, "n_pts 0: %s", dsr_last_error(ctx));
+    /* data association on the same two objects: the points as two detections of world rows (250
+       and 100 of a stride of 250), the tables recounted from dsr_scene_peek; then a 16 x 12 frame
+       against the points form on dsr_frame_inputs_host's rows; the refusals leave the handle usable */
+    {
+      dsr_assoc_params ap;
+      dsr_assoc_params_default(&ap);
+      dsr_assoc_out ao[2], bo[2];
+      int nr[2] = {250, 100}, tab[12], tab2[12];
+      CHECK(dsr_scene_associate_points(sc, &ap, NULL, 2, 250, nr, x, ao, tab) == 0, "%s", dsr_last_error(ctx));
+      CHECK(tab[0] == 250 && tab[2] == 100 && ao[0].n_pts == 250 && ao[1].n_pts == 100, "assoc n_in %d %d", tab[0], tab[2]);
+      int want[12];
+      memset(want, 0, sizeof want);
+      for (int o = 0; o < 2; ++o) {
+        CHECK(dsr_scene_peek(sc, o, n, pidx, px, pf, &cnt) == 0, "%s", dsr_last_error(ctx));
+        for (int j = 0; j < cnt; ++j) {
+          const int d = pidx[j] / 250;
+          CHECK(d == 0 || (d == 1 && pidx[j] < 350), "assoc: a NaN slot is a candidate (%d)", pidx[j]);
+          want[d * 2 + o] += 1;
+          want[4 + d * 2 + o] += fabsf(pf[j]) <= ap.inlier_tol;
+          want[8 + d * 2 + o] += pf[j] < -ap.inlier_tol;
+        }
+      }
+      CHECK(memcmp(tab, want, sizeof tab) == 0, "assoc tables != the recount over peek");
+      CHECK(dsr_assoc_pick_host(&ap, 2, 2, tab, nr, bo) == 0 && memcmp(ao, bo, sizeof ao) == 0, "assoc records != pick_host");
+      CHECK(dsr_scene_stats_get(sc, &sst) == 0 && sst.n_pts == 500 && sst.n_passes == 1 &&
+            sst.decoded == tab[0] + tab[1] + tab[2] + tab[3], "assoc stats");
+      nr[1] = 251;
+      CHECK(dsr_scene_associate_points(sc, &ap, NULL, 2, 250, nr, x, ao, tab2) < 0, "n_rows > max_pts accepted");
+      nr[1] = 100;
+      CHECK(dsr_scene_associate_points(sc, &ap, NULL, 3, 250, nr, x, ao, tab2) < 0, "n_det x max_pts > max_pts accepted");
+      CHECK(dsr_scene_associate_points(sc, &ap, NULL, 0, 250, nr, x, ao, tab2) < 0, "n_det 0 accepted");
+      CHECK(dsr_scene_associate_points(sc, NULL, NULL, 2, 250, nr, x, ao, tab2) < 0, "null parameters accepted");
+      float twc[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+      twc[5] = 1.01f;
+      CHECK(dsr_scene_associate_points(sc, &ap, twc, 2, 250, nr, x, ao, tab2) < 0, "a stretched t_world_cam accepted");
+      twc[5] = 1.f;
+      dsr_assoc_params bad = ap;
+      bad.min_pct = 100;
+      CHECK(dsr_scene_associate_points(sc, &bad, twc, 2, 250, nr, x, ao, tab2) < 0, "min_pct 100 accepted");
+      CHECK(dsr_scene_associate_points(sc, &ap, twc, 2, 250, nr, x, ao, tab2) == 0 && memcmp(tab, tab2, sizeof tab) == 0,
+            "assoc after the refusals (identity t_world_cam): %s", dsr_last_error(ctx));
+      /* the frame: label 3 fills columns 2..13 of rows 1..10 at depth 0.5 with a hole; label 4 is absent */
+      dsr_camera fcam = {16, 12, 16.f, 16.f, 7.5f, 5.5f};
+      dsr_frame_params fp;
+      dsr_frame_params_default(&fp);
+      fp.max_pts = 100; fp.min_mask_area = 10;
+      float fdepth[16 * 12];
+      int finst[16 * 12];
+      for (int v = 0; v < 12; ++v)
+        for (int u = 0; u < 16; ++u) {
+          const int in = v >= 1 && v <= 10 && u >= 2 && u <= 13;
+          finst[v * 16 + u] = in ? 3 : -1;
+          fdepth[v * 16 + u] = in && !(u == 7 && v == 5) ? 0.5f + 0.01f * (float)u : 0.f;
+        }
+      const int labels[2] = {3, 4};
+      int ftab[12], ptab[12];                          /* 3 tables x 2 detections x 2 objects */
+      CHECK(dsr_scene_associate_frame(sc, &fcam, &fp, &ap, twc, fdepth, finst, 2, labels, ao, ftab) == 0, "%s",
+            dsr_last_error(ctx));
+      CHECK(ao[0].n_pts == 100 && ao[0].n_mask == 120 && ao[0].n_valid == 119 && ao[0].ingest_status == DSR_FRAME_OK &&
+            ao[1].status == DSR_ASSOC_NO_POINTS && ao[1].ingest_status == DSR_FRAME_NO_MASK, "assoc frame records %d %d",
+            ao[0].n_pts, ao[1].status);
+      CHECK(ftab[0] == 100, "assoc frame: every row lies in the unit object's ball (%d)", ftab[0]);
+      dsr_frame_det fd[2];
+      memset(fd, 0, sizeof fd);
+      fd[0].label = 3; fd[1].label = 4;
+      fd[0].bbox[2] = fd[0].bbox[3] = fd[1].bbox[2] = fd[1].bbox[3] = -1;
+      float* hp = (float*)calloc(2 * 100 * 3, sizeof(float));
+      float* hr = (float*)calloc(2 * 300 * 3, sizeof(float));
+      float* hz = (float*)calloc(2 * 100, sizeof(float));
+      dsr_frame_det_out fo[2];
+      CHECK(dsr_frame_inputs_host(&fcam, &fp, fdepth, finst, 2, fd, hp, hr, hz, fo) == 0, "frame_inputs_host failed");
+      int fr[2] = {fo[0].n_pts, fo[1].n_pts};
+      CHECK(dsr_scene_associate_points(sc, &ap, twc, 2, 100, fr, hp, bo, ptab) == 0, "%s", dsr_last_error(ctx));
+      CHECK(memcmp(ftab, ptab, sizeof ftab) == 0, "assoc frame tables != the points form on the host rows");
+      CHECK(ao[0].status == bo[0].status && ao[0].obj == bo[0].obj && ao[0].n_hit == bo[0].n_hit && ao[1].status == bo[1].status,
+            "assoc frame records != the points form");
+      CHECK(dsr_scene_associate_frame(sc, &fcam, &fp, &ap, NULL, fdepth, finst, 2, labels, ao, ftab) < 0, "null t_world_cam accepted");
+      fp.max_pts = 251;
+      CHECK(dsr_scene_associate_frame(sc, &fcam, &fp, &ap, twc, fdepth, finst, 2, labels, ao, ftab) < 0, "2 x 251 rows accepted");
+      free(hp); free(hr); free(hz);
+    }
     CHECK(dsr_scene_destroy(sc) == 0, "scene_destroy");
     free(x); free(s0); free(dist); free(g); free(pf); free(px); free(who); free(pidx);
   }

@@ -194,6 +194,21 @@ FRAME_STATUS = {0: "ok", 1: "no pixel carries the label", 2: "mask of at most mi
                 3: "no valid depth in the mask"}
 
 
+class AssocParams(C.Structure):
+    """dsr_assoc_params: every value is taken literally (dsr_assoc_params_default fills the defaults)."""
+    _fields_ = [("inlier_tol", C.c_float), ("min_hits", C.c_int), ("min_pct", C.c_int)]
+
+
+class AssocOut(C.Structure):
+    """dsr_assoc_out: one detection's record of a dsr_scene_associate_* call (include/dsr.h)."""
+    _fields_ = [("status", C.c_int), ("n_pts", C.c_int), ("obj", C.c_int), ("n_hit", C.c_int), ("n_in", C.c_int),
+                ("n_neg", C.c_int), ("second", C.c_int), ("second_hit", C.c_int), ("ingest_status", C.c_int),
+                ("n_mask", C.c_int), ("n_valid", C.c_int)]
+
+
+ASSOC_MATCHED, ASSOC_NEW, ASSOC_NO_POINTS = 0, 1, 2   # include/dsr.h DSR_ASSOC_*
+
+
 class FramePoseParams(C.Structure):
     """dsr_frame_pose_params: every value is taken literally (dsr_frame_pose_params_default fills the
     reference's constants)."""
@@ -371,6 +386,14 @@ SIGNATURES = {
     "dsr_tracker_query": (C.c_int, [C.c_void_p]),
     "dsr_tracker_download": (C.c_int, [C.c_void_p, FP, C.POINTER(TrackOut)]),
     "dsr_lidar_track_prep_host": (C.c_int, [C.POINTER(LidarParams), FP, C.c_int, C.POINTER(LidarDet), FP, FP]),
+    "dsr_assoc_params_default": (C.c_int, [C.POINTER(AssocParams)]),
+    "dsr_scene_associate_frame": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(FrameParams),
+                                            C.POINTER(AssocParams), FP, FP, IP, C.c_int, IP, C.POINTER(AssocOut), IP]),
+    "dsr_scene_associate_points": (C.c_int, [C.c_void_p, C.POINTER(AssocParams), FP, C.c_int, C.c_int, IP, FP,
+                                             C.POINTER(AssocOut), IP]),
+    "dsr_assoc_points_host": (C.c_int, [C.POINTER(Camera), C.POINTER(FrameParams), FP, FP, IP, C.c_int, IP, FP, IP,
+                                        C.POINTER(FrameDetOut)]),
+    "dsr_assoc_pick_host": (C.c_int, [C.POINTER(AssocParams), C.c_int, C.c_int, IP, IP, C.POINTER(AssocOut)]),
 }
 
 #: entry points added without an ABI number change: callers detect them by the symbol, so a
@@ -383,7 +406,9 @@ BY_SYMBOL = ("dsr_reconstruct_views", "dsr_renderer_create", "dsr_renderer_rende
              "dsr_batch_refill_frame_poses", "dsr_batch_frame_pose_info", "dsr_lidar_params_default",
              "dsr_lidar_inputs_host", "dsr_lidar_inputs", "dsr_batch_refill_lidar", "dsr_batch_lidar_info",
              "dsr_tracker_create", "dsr_tracker_destroy", "dsr_tracker_track", "dsr_tracker_track_lidar",
-             "dsr_tracker_query", "dsr_tracker_download", "dsr_lidar_track_prep_host", "dsr_tracker_track_frame")
+             "dsr_tracker_query", "dsr_tracker_download", "dsr_lidar_track_prep_host", "dsr_tracker_track_frame",
+             "dsr_assoc_params_default", "dsr_scene_associate_frame", "dsr_scene_associate_points",
+             "dsr_assoc_points_host", "dsr_assoc_pick_host")
 
 _lib = None
 _lock = threading.RLock()       # re-entrant: Context.get holds it while load_library takes it

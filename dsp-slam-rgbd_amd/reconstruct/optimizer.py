@@ -1110,8 +1110,73 @@ class SceneSdf(object):
                                              C.cast(C.byref(n), L.IP)), "dsr_scene_peek")
         return idx, x, sdf
 
+    def _associated(self, n_det, outs, table):
+        from reconstruct import utils as U
+
+        t = table.reshape(3, n_det, self._n_obj)
+        return ForceKeyErrorDict(records=[U.assoc_record(outs[j]) for j in range(n_det)], n_in=t[0].copy(),
+                                 n_hit=t[1].copy(), n_neg=t[2].copy())
+
+    def associate_frame(self, depth, instance, labels, camera, t_world_cam, **params):
+        """Which of a frame's detections are map objects already seen (dsr_scene_associate_frame;
+        DESIGN.md §3.6d) — Tracking::AssociateObjectsByProjection_onlyformono
+        (src/Tracking_util.cc:210-288) with the depth under each mask as the evidence.  ``labels``:
+        each detection's value in ``instance``; ``camera``: see ``utils.frame_camera``;
+        ``t_world_cam`` (4,4) rigid; ``params``: ``max_pts``, ``min_mask_area``, ``near``, ``far`` of the
+        ingest and ``inlier_tol``, ``min_hits``, ``min_pct`` of the decision.  Returns
+        ``dict(records=[...], n_in=, n_hit=, n_neg=)``: per detection its record
+        (``utils.assoc_record``) and the three (n_det, n_obj) int32 vote tables."""
+        from reconstruct import utils as U
+
+        ctx = self.decoder.ctx
+        if not hasattr(ctx.lib, "dsr_scene_associate_frame"):
+            raise L.DsrError("this libdsr was built without dsr_scene_associate_* (no fallback)")
+        fp, ap = U.assoc_split_params(params)
+        cam = U.frame_camera(camera)
+        depth, instance = U.frame_images(depth, instance, cam)
+        lab = np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
+        n = lab.shape[0]
+        t = np.ascontiguousarray(np.asarray(t_world_cam, np.float32).reshape(16))
+        outs = (L.AssocOut * max(n, 1))()
+        table = np.zeros(3 * n * self._n_obj, np.int32)
+        ctx.check(ctx.lib.dsr_scene_associate_frame(self._handle(), cam, fp, ap, L.fptr(t), L.fptr(depth),
+                                                    L.iptr(instance), n, L.iptr(lab), outs, L.iptr(table)),
+                  "dsr_scene_associate_frame")
+        return self._associated(n, outs, table)
+
+    def associate_points(self, rows, t_world_cam=None, **params):
+        """The same for rows the caller holds (dsr_scene_associate_points), e.g. the LiDAR path's
+        from ``utils.lidar_inputs``.  ``rows``: per detection an (n_j, 3) array of camera-frame
+        points (an empty one is a detection without points); ``t_world_cam`` None: the rows are
+        world points already; ``params``: ``inlier_tol``, ``min_hits``, ``min_pct`` and ``max_pts``,
+        the stride of the detections in the scene's point buffer (default: the longest detection)."""
+        from reconstruct import utils as U
+
+        ctx = self.decoder.ctx
+        if not hasattr(ctx.lib, "dsr_scene_associate_points"):
+            raise L.DsrError("this libdsr was built without dsr_scene_associate_* (no fallback)")
+        params = dict(params)
+        max_pts = params.pop("max_pts", None)
+        fp, ap = U.assoc_split_params(params)
+        arrays = [_f32(r, 3) for r in rows]
+        n = len(arrays)
+        if max_pts is None:
+            max_pts = max([a.shape[0] for a in arrays] + [1])
+        max_pts = int(max_pts)
+        n_rows = np.asarray([a.shape[0] for a in arrays], np.int32).reshape(-1)
+        packed = np.zeros((max(n, 1), max(max_pts, 1), 3), np.float32)
+        for j, a in enumerate(arrays):
+            packed[j, :min(a.shape[0], max(max_pts, 0))] = a[:max(max_pts, 0)]
+        t = None if t_world_cam is None else np.ascontiguousarray(np.asarray(t_world_cam, np.float32).reshape(16))
+        outs = (L.AssocOut * max(n, 1))()
+        table = np.zeros(3 * n * self._n_obj, np.int32)
+        ctx.check(ctx.lib.dsr_scene_associate_points(self._handle(), ap, L.fptr(t), n, max_pts, L.iptr(n_rows),
+                                                     L.fptr(packed), outs, L.iptr(table)),
+                  "dsr_scene_associate_points")
+        return self._associated(n, outs, table)
+
     def stats(self):
-        """dsr_scene_stats of the last ``query`` call, as a dict."""
+        """dsr_scene_stats of the last ``query`` or ``associate_*`` call, as a dict."""
         st = L.SceneStats()
         rc = self.decoder.ctx.lib.dsr_scene_stats_get(self._handle(), C.byref(st))
         if rc != 0:

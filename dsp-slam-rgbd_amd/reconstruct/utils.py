@@ -474,6 +474,104 @@ def lidar_track_prep(detections, t_cam_velo, **params):
     return t[:n], sc[:n]
 
 
+ASSOC_PARAM_NAMES = ("inlier_tol", "min_hits", "min_pct")
+ASSOC_FRAME_PARAM_NAMES = ("max_pts", "min_mask_area", "near", "far")
+
+
+def assoc_params(**params):
+    """``dsr_assoc_params``: the library's defaults (dsr_assoc_params_default: inlier_tol 0.05,
+    min_hits 20, min_pct 50) with ``params`` on top."""
+    from reconstruct import _libdsr as L
+
+    unknown = set(params) - set(ASSOC_PARAM_NAMES)
+    if unknown:
+        raise TypeError(f"unknown association parameters: {sorted(unknown)}")
+    lib = L.load_library()
+    if not hasattr(lib, "dsr_assoc_params_default"):
+        raise L.DsrError("this libdsr was built without dsr_assoc_* (no fallback)")
+    p = L.AssocParams()
+    if lib.dsr_assoc_params_default(p) != 0:
+        raise L.DsrError("dsr_assoc_params_default failed")
+    for k, v in params.items():
+        setattr(p, k, float(v) if k == "inlier_tol" else int(v))
+    return p
+
+
+def assoc_split_params(params):
+    """``params`` of an association call -> (``dsr_frame_params`` of the ingest fields it reads,
+    ``dsr_assoc_params``)."""
+    unknown = set(params) - set(ASSOC_PARAM_NAMES) - set(ASSOC_FRAME_PARAM_NAMES)
+    if unknown:
+        raise TypeError(f"unknown association parameters: {sorted(unknown)}")
+    return (frame_params(**{k: v for k, v in params.items() if k in ASSOC_FRAME_PARAM_NAMES}),
+            assoc_params(**{k: v for k, v in params.items() if k in ASSOC_PARAM_NAMES}))
+
+
+def assoc_record(o):
+    """A ``dsr_assoc_out`` as a dict."""
+    return ForceKeyErrorDict(status=int(o.status), n_pts=int(o.n_pts), obj=int(o.obj), n_hit=int(o.n_hit),
+                             n_in=int(o.n_in), n_neg=int(o.n_neg), second=int(o.second),
+                             second_hit=int(o.second_hit), ingest_status=int(o.ingest_status), n_mask=int(o.n_mask),
+                             n_valid=int(o.n_valid))
+
+
+def assoc_points(depth, instance, labels, camera, t_world_cam, **params):
+    """The points ``SceneSdf.associate_frame`` queries, on the host (``dsr_assoc_points_host``: plain
+    C++, no device): every label's surface-point rows of the depth image moved to
+    the world by ``t_world_cam``, at the fixed stride ``max_pts`` with NaN beyond a detection's
+    count — the evidence that stands in for the map points of src/Tracking_util.cc:210-288.
+    ``params``: ``max_pts``, ``min_mask_area``, ``near``, ``far``.  Returns ``(pts_world (n_det,
+    max_pts, 3), n_rows (n_det,), records)`` with the ingest records of ``frame_record``."""
+    from reconstruct import _libdsr as L
+
+    lib = L.load_library()
+    if not hasattr(lib, "dsr_assoc_points_host"):
+        raise L.DsrError("this libdsr was built without dsr_assoc_* (no fallback)")
+    unknown = set(params) - set(ASSOC_FRAME_PARAM_NAMES)
+    if unknown:
+        raise TypeError(f"unknown association frame parameters: {sorted(unknown)}")
+    p = frame_params(**params)
+    cam = frame_camera(camera)
+    depth, instance = frame_images(depth, instance, cam)
+    lab = np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
+    n = lab.shape[0]
+    t = np.ascontiguousarray(np.asarray(t_world_cam, np.float32).reshape(16))
+    pts = np.zeros((max(n, 1), max(p.max_pts, 1), 3), np.float32)
+    n_rows = np.zeros(max(n, 1), np.int32)
+    out = (L.FrameDetOut * max(n, 1))()
+    rc = lib.dsr_assoc_points_host(cam, p, L.fptr(t), L.fptr(depth), L.iptr(instance), n, L.iptr(lab), L.fptr(pts),
+                                   L.iptr(n_rows), out)
+    if rc != 0:
+        raise L.DsrError(f"dsr_assoc_points_host failed ({rc}): bad camera, image, labels, frame parameters or "
+                         "t_world_cam")
+    return pts[:n], n_rows[:n], [frame_record(out[i]) for i in range(n)]
+
+
+def assoc_pick(n_in, n_hit, n_neg, n_rows, **params):
+    """The decision of ``SceneSdf.associate_*`` from the vote tables, on the host
+    (``dsr_assoc_pick_host``; DESIGN.md §3.6d — the winner of the vote of
+    src/Tracking_util.cc:210-288): ``n_in``, ``n_hit``, ``n_neg`` (n_det, n_obj) int32, ``n_rows``
+    (n_det,) the detections' row counts; ``params``: ``ASSOC_PARAM_NAMES``.  Returns the records."""
+    from reconstruct import _libdsr as L
+
+    lib = L.load_library()
+    if not hasattr(lib, "dsr_assoc_pick_host"):
+        raise L.DsrError("this libdsr was built without dsr_assoc_* (no fallback)")
+    p = assoc_params(**params)
+    n_rows = np.ascontiguousarray(np.asarray(n_rows, np.int32).reshape(-1))
+    n = n_rows.shape[0]
+    tabs = [np.asarray(t, np.int32) for t in (n_in, n_hit, n_neg)]
+    n_obj = tabs[0].shape[1] if tabs[0].ndim == 2 else -1
+    if any(t.shape != (n, n_obj) for t in tabs):
+        raise ValueError("n_in, n_hit and n_neg must share the shape (n_det, n_obj)")
+    table = np.ascontiguousarray(np.stack(tabs)).reshape(-1)
+    out = (L.AssocOut * max(n, 1))()
+    rc = lib.dsr_assoc_pick_host(p, n, n_obj, L.iptr(table) if table.size else None, L.iptr(n_rows), out)
+    if rc != 0:
+        raise L.DsrError(f"dsr_assoc_pick_host failed ({rc}): bad parameters, tables or counts")
+    return [assoc_record(out[i]) for i in range(n)]
+
+
 def create_voxel_grid(vol_dim=128):
     """utils.py:97-116.  Note the reference's ``LongTensor / vol_dim`` is TRUE division
     in torch >= 1.6 (fp32), so its x/y columns are not integer lattice indices; this

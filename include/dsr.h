@@ -983,6 +983,94 @@ int dsr_tracker_download(dsr_tracker* tr, float* t_out, dsr_track_out* rec);
 int dsr_lidar_track_prep_host(const dsr_lidar_params* params, const float* t_cam_velo, int n_det,
                               const dsr_lidar_det* dets, float* t_co_se3, float* det_scale);
 
+/* ---- data association: which of a frame's detections are map objects already seen (DESIGN.md
+ * 3.6d states the rule exactly).  Replaces Tracking::AssociateObjectsByProjection_onlyformono
+ * (src/Tracking_util.cc:210-288), which votes per detection over the object ids of the ORB map
+ * points under its mask; ORB-SLAM's map is outside this library, so the evidence here is the depth
+ * under the mask and the map's decoders: a detection belongs to the map object whose surface its
+ * back-projected points lie on.  Callers detect these entry points by symbol; the ABI number is
+ * unchanged.
+ *
+ * Detection j has n_pts_j camera-frame rows q (from a frame: exactly the surface-point rows
+ * DESIGN.md 3.5b gives its label, the points-only ingest of dsr_tracker_track_frame; from host
+ * rows: the caller's).  World point w_k = fmaf(B_k0, q_x, fmaf(B_k1, q_y, fmaf(B_k2, q_z, b_k)))
+ * with B | b rows 0..2 of t_world_cam, which must be rigid (last row 0 0 0 1, R^T R = I within
+ * 1e-4, det R > 0).  Row k of detection j is scene point p = j max_pts + k; slots k >= n_pts_j
+ * hold NaN (in no ball); the detection of a point is p / max_pts.  Candidates and decoded values
+ * f are exactly dsr_scene_query's on those points.  Three int32 tables [n_det][n_obj]: n_in, the
+ * detection's candidates of the object; n_hit, those with fabsf(f) <= inlier_tol (object units,
+ * fp32; a NaN f counts in n_in only); n_neg, those with f < -inlier_tol (the measured surface lies
+ * inside the model: evidence against the match).  Every detection decides on its own: the best
+ * object is the first with the largest n_hit, the runner-up the first of the others with the
+ * largest n_hit; the detection is DSR_ASSOC_MATCHED iff n_hit >= min_hits and 100 n_hit > min_pct
+ * n_pts_j (integers), else DSR_ASSOC_NEW; n_pts_j == 0 is DSR_ASSOC_NO_POINTS. */
+typedef struct {
+  float inlier_tol;               /* |f| at most this is a hit (0.05: reconstruct/optimizer.py:78) */
+  int min_hits;                   /* hits a match needs at least (20: src/Tracking_util.cc:199) */
+  int min_pct;                    /* ... and more than this percentage of the detection's rows (50) */
+} dsr_assoc_params;
+enum {
+  DSR_ASSOC_MATCHED = 0,          /* obj is the map object (the mpMapObjects hit of src/Tracking_util.cc:210-288) */
+  DSR_ASSOC_NEW = 1,              /* no object passed: a new object (src/Tracking_util.cc:210-288, the isNew branch) */
+  DSR_ASSOC_NO_POINTS = 2         /* n_pts == 0; a frame detection whose ingest status is not DSR_FRAME_OK */
+};
+typedef struct {
+  int status;                     /* DSR_ASSOC_* */
+  int n_pts;                      /* the detection's rows */
+  int obj;                        /* the matched object; -1 unless DSR_ASSOC_MATCHED */
+  int n_hit, n_in, n_neg;         /* the best object's counts, accepted or not (0 on an empty map) */
+  int second, second_hit;         /* the runner-up and its n_hit (-1, 0 with fewer than two objects) */
+  int ingest_status;              /* a frame call: DSR_FRAME_* of the detection; host rows: 0 */
+  int n_mask, n_valid;            /* a frame call: those of dsr_frame_det_out; host rows: 0 */
+} dsr_assoc_out;
+/* Host only: inlier_tol 0.05, min_hits 20, min_pct 50 (the thresholds of
+ * src/Tracking_util.cc:210-288's callers, see the fields).  Every other call takes the values
+ * literally. */
+int dsr_assoc_params_default(dsr_assoc_params* p);
+/* The association of src/Tracking_util.cc:210-288 for the n_det detections of a depth image and
+ * its instance labels against the map of dsr_scene_set_objects, in one call on the device: the
+ * images and labels go through a pinned block of the scene (it grows with the largest image seen)
+ * in one upload, the frame ingest's kernels write the rows, k_assoc_world the world points, the
+ * scene's value passes decode the candidates, k_assoc_vote / k_assoc_pick (csrc/dsr_assoc.hpp)
+ * write the tables and the records; the host waits once, at the end.  Of frame_params only
+ * max_pts, min_mask_area, near and far are read.  out: n_det records; table: NULL or 3 n_det n_obj
+ * ints in the order n_in, n_hit, n_neg.  Afterwards dsr_scene_peek and dsr_scene_stats_get speak
+ * of this call's n_det max_pts points.  Errors, returned before the device is touched (the handle
+ * stays usable): null arguments, a call before dsr_scene_set_objects, n_det < 1, n_det max_pts
+ * above the scene's max_pts, a non-rigid or non-finite t_world_cam, the argument errors of
+ * dsr_frame_inputs_host for the fields that are read, inlier_tol not positive and finite,
+ * min_hits < 1, min_pct outside 0..99.  A map of zero objects is no error: every detection is
+ * DSR_ASSOC_NEW or DSR_ASSOC_NO_POINTS and the tables are empty.  Threads: a dsr_scene handle is
+ * single-threaded — its calls (set_objects, query, peek, associate_*) share the handle's point,
+ * pass and staging buffers and must not overlap; the associate calls additionally hold the
+ * context's run lock, as the tracker's calls do, so they are ordered against other handles' runs
+ * on the context stream.  A HIP error in the middle of a call drains the stream before it is
+ * returned: no copy out of the pinned blocks is left in flight. */
+int dsr_scene_associate_frame(dsr_scene* sc, const dsr_camera* cam, const dsr_frame_params* frame_params,
+                              const dsr_assoc_params* assoc_params, const float* t_world_cam,
+                              const float* depth, const int* instance, int n_det, const int* labels,
+                              dsr_assoc_out* out, int* table);
+/* The same (src/Tracking_util.cc:210-288) for rows the caller holds, e.g. the LiDAR path's from
+ * dsr_lidar_inputs: rows is n_det x max_pts x 3 camera-frame floats of which n_rows[j] rows count
+ * for detection j; t_world_cam NULL: the rows are world points already and are taken as they are.
+ * Errors as above, and n_rows[j] outside 0..max_pts. */
+int dsr_scene_associate_points(dsr_scene* sc, const dsr_assoc_params* assoc_params, const float* t_world_cam,
+                               int n_det, int max_pts, const int* n_rows, const float* rows,
+                               dsr_assoc_out* out, int* table);
+/* Host only, no context, no device: the points dsr_scene_associate_frame queries (the evidence
+ * that stands in for the map points of src/Tracking_util.cc:210-288) — the frame's rows
+ * transformed into pts_world (n_det x max_pts x 3, NaN beyond a detection's count), the counts
+ * n_rows (n_det) and, unless NULL, the ingest records (those of dsr_frame_inputs_host at max_bg 0,
+ * downsample 1, expand 0 and the mask's tight box).  Returns -2 for a bad argument. */
+int dsr_assoc_points_host(const dsr_camera* cam, const dsr_frame_params* frame_params, const float* t_world_cam,
+                          const float* depth, const int* instance, int n_det, const int* labels,
+                          float* pts_world, int* n_rows, dsr_frame_det_out* ingest);
+/* Host only: the decision of src/Tracking_util.cc:210-288's vote from the tables (3 n_det n_obj
+ * ints: n_in, n_hit, n_neg; NULL allowed when n_obj == 0) and the detections' row counts.  The
+ * ingest fields of the records are 0.  Returns -2 for a bad argument. */
+int dsr_assoc_pick_host(const dsr_assoc_params* assoc_params, int n_det, int n_obj, const int* table,
+                        const int* n_rows, dsr_assoc_out* out);
+
 #ifdef __cplusplus
 }
 #endif
