@@ -80,8 +80,8 @@ static float* ln_workspace(dsr_ctx* ctx, int g) {
 // bit3 split-fp16; 12 = split-fp16 + setprio, the default) and the A-ring depth of the split
 // kernels (DSR_SPLIT_RING: 0 = the two-set gemm16_tile, 2..4 = gemm16_ring k steps in flight)
 // Kernel-selecting switches (A/B experiments: DSR_FWD_VARIANT, DSR_JAC_VARIANT, DSR_SPLIT_RING,
-// DSR_LITE_VARIANT, DSR_LITE_LAG, DSR_REFINE_ALL, DSR_RENDER_PASSES, DSR_KEEP_MASKS,
-// DSR_SURFACE_EXACT) and the test hooks are read from the environment only under
+// DSR_LITE_VARIANT, DSR_LITE_LAG, DSR_REFINE_ALL, DSR_RENDER_PASSES, DSR_ADAPTIVE_WINDOWS,
+// DSR_KEEP_MASKS, DSR_SURFACE_EXACT) and the test hooks are read from the environment only under
 // DSR_TEST_HOOKS=1, which dsr_stats.test_hooks reports: a stray variable cannot change the kernels
 // of a production run (test_gpu_lite_audit.py: test_kernel_switches_ignored_without_the_gate).
 // The two production switches, DSR_STREAMS (object groups) and DSR_GRAPH (graph replay), are
@@ -1155,6 +1155,25 @@ static std::vector<int> render_passes(int M, long samples, long rays, int n_cu) 
   r.push_back(M);
   return r;
 }
+// Per-object render-pass windows (choose_windows, dsr_kernels.hpp): on by default
+// for a lite batch on its default multi-pass schedule.  Under DSR_TEST_HOOKS=1
+// DSR_ADAPTIVE_WINDOWS=0 keeps the fixed windows; an explicit DSR_RENDER_PASSES keeps its fixed
+// windows too unless DSR_ADAPTIVE_WINDOWS=1 is set beside it (the windows then start from that
+// schedule).  Returns the pass count the objects re-choose windows for, 0: fixed windows.
+static int adaptive_windows(const std::vector<int>& passes, bool lite) {
+  const int np = (int)passes.size() - 1;
+  if (!lite || np < 2 || np + 1 > WIN_MAX) return 0;
+  const char* e = hook_env("DSR_ADAPTIVE_WINDOWS");
+  const bool on = e ? atoi(e) != 0 : hook_env("DSR_RENDER_PASSES") == nullptr;
+  return on ? np : 0;
+}
+static WinTable win_table(const std::vector<int>& passes) {
+  WinTable w{};
+  if ((int)passes.size() > WIN_MAX) return w;    // (a longer explicit schedule: kernel arguments only)
+  w.n = (int)passes.size();
+  for (int i = 0; i < w.n; ++i) w.b[i] = (unsigned char)passes[i];
+  return w;
+}
 static size_t ev_per_iter(const dsr_batch* b) { return 2 * (b->passes.size() - 1 + (b->lite ? 1 : 0)) + 2; }
 
 // A batch buffer: the smallest pooled block that fits (and wastes at most half of itself
@@ -1223,6 +1242,7 @@ static GNParams make_params(const dsr_optim_params* p, bool hooks) {
   P.b1 = p->b1; P.b2 = p->b2; P.lr = p->lr; P.s_damp = p->s_damp;
   P.cut_off = p->cut_off; P.iters = p->num_iterations; P.M = p->num_depth_samples;
   P.raw_residual = 0;
+  P.n_win = 0;                                   // (a batch sets it: adaptive_windows)
   // lite-pass margin: th in the first iteration, then max(0.002, 4 x the
   // largest |lite - exact| the object's band and audit samples showed; the audit guards it).
   // DSR_LITE_MARGIN / _FLOOR / _SAFETY only under DSR_TEST_HOOKS=1 (lite_settings)
@@ -1615,6 +1635,7 @@ static int batch_create_impl(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_opt
     hipMemsetAsync(b->tr_i, 0, sizeof(int) * TRACE_I_STRIDE * std::max(1, b->iters) * n_obj, ctx->stream);
   }
   b->passes = render_passes(M, (long)cand_off, (long)ray_off, ctx->n_cu);
+  b->P.n_win = adaptive_windows(b->passes, b->lite);
   b->ev.resize((size_t)std::max(1, b->loop_iters) * b->groups.size() * ev_per_iter(b) + 2);
   b->join_ev.resize(b->groups.size());
   for (auto& e : b->ev)
@@ -2264,20 +2285,21 @@ static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
                                          (size_t)(gr.c1 - gr.c0), s));   // out-of-ball samples: NaN
       for (int pz = 0; pz < np; ++pz) {          // render passes with early ray termination
         const int ra = b->passes[pz], rb = b->passes[pz + 1];
+        const int wz = P.n_win ? pz : -1;        // the objects' own windows for this pass, or [ra, rb)
         if (chunked) {                           // count (the first pass: the ray scan), then emit
           if (pz == 0)
             hipLaunchKernelGGL(k_sample_scan, dim3(gr.n_rch), dim3(RENDER_RAYS), 0, s, gr.rchunks, desc, st, b->rays,
-                               b->M, rb, b->dead, b->rinfo, b->rwin, gr.scnt, b->dense);
+                               b->M, rb, wz, b->dead, b->rinfo, b->rwin, gr.scnt, b->dense);
           else
             hipLaunchKernelGGL(k_sample_count, dim3(gr.n_rch), dim3(RENDER_RAYS), 0, s, gr.rchunks, desc, st, b->rays,
-                               b->M, ra, rb, b->dead, b->rinfo, b->rwin, gr.scnt);
+                               b->M, ra, rb, wz, b->dead, b->rinfo, b->rwin, gr.scnt);
           // (+1 workgroup: the pass's tile table, from the count kernel's chunk counts)
           hipLaunchKernelGGL(k_sample_emit, dim3(gr.n_rch + 1), dim3(RENDER_RAYS), 0, s, gr.rchunks, desc, st,
-                             b->rays, b->M, ra, rb, b->cand, b->rwin, gr.scnt,
+                             b->rays, b->M, ra, rb, wz, b->cand, b->rwin, gr.scnt,
                              ChunkTiles{gr.och, gr.tiles_f, gr.nt_f, ng, b->lite ? LTILE : TILE, 0});
         } else {
           hipLaunchKernelGGL(k_sample_pass, dim3(ng), dim3(SAMPLE_THREADS), 0, s, ng, desc, st, b->rays, b->M,
-                             ra, rb, b->cand, b->dead, b->rinfo);
+                             ra, rb, wz, b->cand, b->dead, b->rinfo);
           hipLaunchKernelGGL(k_tiles_fwd, dim3(1), dim3(1024), 0, s, ng, desc, st, gr.tiles_f, gr.nt_f,
                              b->lite ? LTILE : TILE, 0);
         }
@@ -2295,8 +2317,8 @@ static int batch_enqueue_iters(dsr_batch* b, bool timing, int it0, int it1) {
       if (b->lite) {                             // exact split-fp16 decode of the band samples
         if (rays) {
           hipLaunchKernelGGL(k_refine_scan, dim3(gr.n_rch), dim3(REFINE_SCAN_THREADS), 0, s, gr.rchunks, desc, st, b->M,
-                             b->refine, refine_all() ? nullptr : b->dense, -P.cut_off, b->rbits, b->abits, gr.ccnt,
-                             b->ma.slotmap);
+                             b->refine, b->dense, refine_all() ? 1 : 0, -P.cut_off, b->rbits, b->abits, gr.ccnt,
+                             b->ma.slotmap, P.n_win);
           const int wp = (b->ma.pts && fv == 12) ? 1 : 0;   // (chunked: +1 workgroup, the exact pass's tiles)
           hipLaunchKernelGGL(k_refine_emit, dim3(gr.n_rch + (chunked ? 1 : 0)), dim3(RENDER_RAYS), 0, s, gr.rchunks,
                              desc, st, b->rays, b->M, b->cand, b->ma.slotmap, b->rbits, b->abits, gr.ccnt,
@@ -2369,7 +2391,7 @@ static int batch_enqueue(dsr_batch* b, bool timing = true) {
   const int n = b->n_obj;
   if (timing) DSR_CHECK(ctx, hipEventRecord(b->ev[0], ctx->stream));
   hipLaunchKernelGGL(k_init_state, dim3(n), dim3(64), 0, ctx->stream, n, b->t_in, b->is_oc, b->z_in, b->st,
-                     b->zbuf, b->iters);
+                     b->zbuf, b->iters, win_table(b->passes));
   DSR_CHECK(ctx, hipMemsetAsync(b->diag, 0, sizeof(int) * STD_INTS, ctx->stream));
   if (b->n_tied) DSR_CHECK(ctx, hipMemsetAsync(b->fail_view, 0xff, sizeof(int) * b->n_tied, ctx->stream));
   if (b->tie_multi)               // the views' start poses from their leaders' (before the groups fork)
@@ -2640,6 +2662,25 @@ int dsr_exp_prov(dsr_batch* b, int* alive, float* y, int* set, int* xcc, int* R,
   return 0;
 }
 #endif
+int dsr_batch_windows(dsr_batch* b, int* adaptive, int* n_bounds, int* bounds) {
+  if (!b || !adaptive || !n_bounds) return -2;
+  *adaptive = b->P.n_win > 0 ? 1 : 0;
+  *n_bounds = (int)b->passes.size();
+  if (!bounds) return 0;
+  if (!b->ran) return fail(b->ctx, "batch has not run");
+  hipSetDevice(b->ctx->device);
+  {
+    const int rc = batch_finish(b);
+    if (rc) return rc;
+  }
+  std::vector<ObjState> hs(b->n_obj);
+  DSR_CHECK(b->ctx, hipMemcpy(hs.data(), b->st, sizeof(ObjState) * hs.size(), hipMemcpyDeviceToHost));
+  for (int o = 0; o < b->n_obj; ++o)
+    for (int i = 0; i < *n_bounds; ++i)       // (a schedule too long for the table: the fixed one)
+      bounds[(size_t)o * *n_bounds + i] = *n_bounds <= WIN_MAX ? hs[o].win[i] : b->passes[i];
+  return 0;
+}
+
 int dsr_batch_lite_diag(dsr_batch* b, int* rec, int n) {
   if (!b || !rec || n < 0) return -2;
   if (!b->ran) return fail(b->ctx, "batch has not run");
@@ -4545,7 +4586,7 @@ int dsr_pose_only_batch(dsr_ctx* ctx, const dsr_decoder* dec, const dsr_optim_pa
   P.raw_residual = 1;
   fold_codes(s, D, dz, n_obj, db0, db4);
   hipLaunchKernelGGL(k_init_state, dim3(n_obj), dim3(64), 0, s, n_obj, (const float*)dtin, (const int*)doc,
-                     (const float*)dz, dst, dzb, 1);                                   // :57 t_obj_cam = inv
+                     (const float*)dz, dst, dzb, 1, WinTable{});                       // :57 t_obj_cam = inv
   int n_tiles = 0;
   // points, descriptors and tile table of the current point sets (objects back to back)
   auto upload = [&]() {
@@ -4825,7 +4866,7 @@ static int track_run(dsr_tracker* tr, int n, size_t pts_floats, int tile_bound, 
   const DevDecoder& D = tr->dec->D;
   fold_codes(s, D, tr->z, n, tr->b0, tr->b4);
   hipLaunchKernelGGL(k_init_state, dim3(n), dim3(64), 0, s, n, (const float*)tr->t_in, (const int*)tr->is_oc,
-                     (const float*)tr->z, tr->st, tr->zb, 1);                          // :57 t_obj_cam = inv
+                     (const float*)tr->z, tr->st, tr->zb, 1, WinTable{});              // :57 t_obj_cam = inv
   JacQuery jq{tr->tiles, tr->n_tiles, tr->desc, tr->b0, tr->b4};
   jq.st = tr->st;
   jq.surf_pts = tr->pts;

@@ -115,6 +115,14 @@ struct ObjDesc {
 
 enum { ST_RUNNING = 0, ST_DONE = 1, ST_FAIL = 2 };
 
+// Render-pass windows: at most WIN_MAX - 1 passes have a per-object table (a longer explicit
+// DSR_RENDER_PASSES schedule stays fixed).  WinTable: the batch's fixed boundaries, by value.
+constexpr int WIN_MAX = 16;
+struct WinTable {
+  int n;                 // boundaries (passes + 1), 0: none
+  unsigned char b[WIN_MAX];
+};
+
 struct ObjState {
   float T[16];           // t_obj_cam (camera -> object), row-major
   float Tco[16];         // inverse(T) of this iteration (optimizer.py:122)
@@ -136,7 +144,14 @@ struct ObjState {
   int lite_viol;         // this iteration's audited samples whose exact class differs
   int lite_viol_total;   // over the run
   int lite_redo;         // 1: an iteration was discarded for a violation; exact from then on
-  int pad_[8];           // whole 128 B lines per object: no line holds two groups' objects
+  // Per-object render-pass windows (k_sample_*): in-ball-rank boundaries win[0] = 0 < win[1] <
+  // ... < win[P] = M, the batch's fixed schedule at k_init_state, re-chosen by k_solve from hist
+  // when the batch adapts its windows (GNParams.n_win > 0; choose_windows, dsr_kernels.hpp)
+  unsigned char win[WIN_MAX];
+  int pad_[4];           // whole 128 B lines per object: no line holds two groups' objects
+  // this iteration's rays by the in-ball rank of their first certainly-full sample
+  // (k_refine_scan; bin M - 1 also counts the rays that never terminate)
+  int hist[MAXM];
 };
 static_assert(sizeof(ObjState) % 128 == 0, "ObjState spans whole cache lines");
 
@@ -305,6 +320,8 @@ struct GNParams {
   float lite_margin0;    // lite pass: first-iteration margin
   float lite_floor;      // ... smallest margin
   float lite_safety;     // ... margin = max(floor, safety x max observed lite error)
+  int n_win;             // render passes whose windows each object re-chooses per iteration
+                         // (choose_windows), 0: the batch's fixed windows
 };
 
 // (p[...,None,:] * T[:3,:3]).sum(-1) + T[:3,3]   (loss.py:31-32, :74-77)

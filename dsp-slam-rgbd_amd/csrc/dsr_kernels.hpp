@@ -201,7 +201,8 @@ __device__ void exp_se3_dev(const float* x, float* out) {
 // state init / per-iteration prologue
 // ------------------------------------------------------------------------------------
 __global__ void k_init_state(int n_obj, const float* __restrict__ t_in, const int* __restrict__ is_oc,
-                             const float* __restrict__ z_in, ObjState* st, float* zbuf, int iters) {
+                             const float* __restrict__ z_in, ObjState* st, float* zbuf, int iters,
+                             WinTable win) {
   const int o = blockIdx.x;
   if (o >= n_obj) return;
   if (threadIdx.x < CODE) zbuf[o * CODE + threadIdx.x] = z_in[o * CODE + threadIdx.x];
@@ -222,6 +223,7 @@ __global__ void k_init_state(int n_obj, const float* __restrict__ t_in, const in
     S.sdf_loss = S.render_loss = 0.f;
     S.lite_margin = S.lite_err = 0.f;
     S.n_audit = S.lite_viol = S.lite_viol_total = S.lite_redo = 0;
+    for (int i = 0; i < WIN_MAX; ++i) S.win[i] = i < win.n ? win.b[i] : 0;   // the batch's fixed windows
   }
 }
 
@@ -236,6 +238,7 @@ __global__ __launch_bounds__(512) void k_iter_begin(int n_obj, const ObjDesc* __
   const int tid = threadIdx.x;
   __shared__ float z[CODE];
   if (tid < CODE) z[tid] = zbuf[o * CODE + tid];
+  if (P.n_win && tid < MAXM) S.hist[tid] = 0;                  // (k_refine_scan counts, k_solve reads)
   __syncthreads();
   for (int n = tid; n < HID; n += blockDim.x) {
     float s0 = 0.f, s4 = 0.f;
@@ -328,7 +331,10 @@ __device__ __forceinline__ float3 ray_sample(const float3 r, const SampleLds& L,
 // exact zero, and its de_do = 0 fails the 1e-2 filter (:135): decoding it cannot change
 // any output, and k_render sees it only behind T == 0.  Results are bit-identical to
 // decoding every in-ball sample; the first pass also marks the out-of-ball samples (NaN)
-// and counts n_valid (loss.py:82-88) over ALL in-ball samples.
+// and counts n_valid (loss.py:82-88) over ALL in-ball samples.  The window of pass pz is the
+// kernel arguments' [ra, rb) for every object, or (pz >= 0) each object's own
+// [win[pz], win[pz + 1]) (ObjState.win, choose_windows): which samples BEHIND a ray's first
+// certainly-full one are decoded is all a window decides, so the results are those bits either way.
 // One thread per ray, (ray, depth)-ordered output (k_sample_scan / _count / _emit below).
 // ------------------------------------------------------------------------------------
 // Ray chunks: k_refine_* and k_render_* run one workgroup per RENDER_RAYS rays of an object
@@ -588,12 +594,13 @@ __global__ __launch_bounds__(RENDER_RAYS) DSR_NO_PK_F32 void k_sample_scan(const
                                                              const ObjDesc* __restrict__ desc,
                                                              const ObjState* __restrict__ st,
                                                              const float* __restrict__ rays_all, int M, int rb,
-                                                             int* __restrict__ dead, int* __restrict__ rinfo,
+                                                             int pz, int* __restrict__ dead, int* __restrict__ rinfo,
                                                              int* __restrict__ rwin, int* __restrict__ sc,
                                                              float* __restrict__ dense) {
   const RenderChunk ch = chunks[blockIdx.x];
   const ObjState& S = st[ch.obj];
   if (S.status != ST_RUNNING) return;
+  if (pz >= 0) rb = S.win[pz + 1];           // the object's own window (ObjState.win)
   const ObjDesc d = desc[ch.obj];
   __shared__ SampleLds L;
   stage_samples(L, S, M, threadIdx.x);
@@ -646,12 +653,13 @@ __global__ __launch_bounds__(RENDER_RAYS) DSR_NO_PK_F32 void k_sample_count(cons
                                                               const ObjDesc* __restrict__ desc,
                                                               const ObjState* __restrict__ st,
                                                               const float* __restrict__ rays_all, int M, int ra,
-                                                              int rb, int* __restrict__ dead,
+                                                              int rb, int pz, int* __restrict__ dead,
                                                               const int* __restrict__ rinfo,
                                                               int* __restrict__ rwin, int* __restrict__ sc) {
   const RenderChunk ch = chunks[blockIdx.x];
   const ObjState& S = st[ch.obj];
   if (S.status != ST_RUNNING) return;
+  if (pz >= 0) { ra = S.win[pz]; rb = S.win[pz + 1]; }
   const ObjDesc d = desc[ch.obj];
   __shared__ SampleLds L;
   stage_samples(L, S, M, threadIdx.x);
@@ -684,7 +692,7 @@ __global__ __launch_bounds__(RENDER_RAYS) DSR_NO_PK_F32 void k_sample_count(cons
 __global__ __launch_bounds__(RENDER_RAYS) DSR_NO_PK_F32 void k_sample_emit(const RenderChunk* __restrict__ chunks,
                                                              const ObjDesc* __restrict__ desc, ObjState* st,
                                                              const float* __restrict__ rays_all, int M, int ra,
-                                                             int rb, float4* __restrict__ cand,
+                                                             int rb, int pz, float4* __restrict__ cand,
                                                              const int* __restrict__ rwin,
                                                              const int* __restrict__ sc, ChunkTiles T) {
   if (T.och && (int)blockIdx.x == (int)gridDim.x - 1) {   // the extra workgroup: the pass's tile table
@@ -694,6 +702,7 @@ __global__ __launch_bounds__(RENDER_RAYS) DSR_NO_PK_F32 void k_sample_emit(const
   const RenderChunk ch = chunks[blockIdx.x];
   ObjState& S = st[ch.obj];
   if (S.status != ST_RUNNING) return;
+  if (pz >= 0) { ra = S.win[pz]; rb = S.win[pz + 1]; }     // (win[0] = 0: ra == 0 is still the first pass)
   const ObjDesc d = desc[ch.obj];
   __shared__ int wsum[RENDER_RAYS / 64];
   __shared__ SampleLds L;
@@ -758,11 +767,13 @@ __global__ __launch_bounds__(RENDER_RAYS) DSR_NO_PK_F32 void k_sample_emit(const
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SAMPLE_THREADS) DSR_NO_PK_F32 void k_sample_pass(int n_obj, const ObjDesc* __restrict__ desc,
                                                                 ObjState* st, const float* __restrict__ rays_all,
-                                                                int M, int ra, int rb, float4* __restrict__ cand,
+                                                                int M, int ra, int rb, int pz,
+                                                                float4* __restrict__ cand,
                                                                 int* __restrict__ dead, int* __restrict__ rinfo) {
   const int o = blockIdx.x;
   ObjState& S = st[o];
   if (S.status != ST_RUNNING) return;
+  if (pz >= 0) { ra = S.win[pz]; rb = S.win[pz + 1]; }     // the object's own window (ObjState.win)
   const ObjDesc d = desc[o];
   const float* rays = rays_all + (size_t)d.ray_off * 3;
   const bool first = ra == 0;
@@ -869,17 +880,22 @@ __global__ __launch_bounds__(SAMPLE_THREADS) DSR_NO_PK_F32 void k_sample_pass(in
 // (loss.py:111-135) multiplied by that zero (the early-termination argument, DESIGN
 // §3.3) — band samples there need no exact value.  Every sample in front of it was
 // decoded by this iteration's passes (in-ball rank = depth order), and out-of-ball
-// samples hold NaN, so the scan reads only this iteration's values.  `dense` == nullptr
-// refines every flagged sample (DSR_REFINE_ALL=1).
+// samples hold NaN, so the scan reads only this iteration's values.  `all` refines every
+// flagged sample (DSR_REFINE_ALL=1).
+// `adapt` (per-object render-pass windows, choose_windows): the scan also counts the object's
+// rays by the in-ball rank of that first certainly-full sample into ObjState.hist — every
+// in-ball sample in front of it was decoded, so the rank is the number of non-NaN values before
+// it; a ray that never terminates counts in bin M - 1.  One LDS histogram per chunk, one
+// atomic add per non-empty bin: integer counts, the same sums in any order.
 // ------------------------------------------------------------------------------------
 constexpr int REFINE_SCAN_THREADS = 256;   // 4 waves x 32 rays of a chunk: one round of loads each
 __global__ __launch_bounds__(REFINE_SCAN_THREADS) void k_refine_scan(const RenderChunk* __restrict__ chunks,
                                                              const ObjDesc* __restrict__ desc, ObjState* st,
                                                              int M, unsigned char* __restrict__ refine,
-                                                             const float* __restrict__ dense, float nth,
+                                                             const float* __restrict__ dense, int all, float nth,
                                                              uint64_t* __restrict__ rbits_g,
                                                              uint64_t* __restrict__ abits_g, int* __restrict__ ccnt,
-                                                             int* __restrict__ slotmap) {
+                                                             int* __restrict__ slotmap, int adapt) {
   const RenderChunk ch = chunks[blockIdx.x];
   ObjState& S = st[ch.obj];
   if (S.status != ST_RUNNING) return;
@@ -887,8 +903,13 @@ __global__ __launch_bounds__(REFINE_SCAN_THREADS) void k_refine_scan(const Rende
   constexpr int NW = REFINE_SCAN_THREADS / 64, RPW = RENDER_RAYS / NW;   // waves, rays per wave
   __shared__ uint64_t rbits[RENDER_RAYS], abits[RENDER_RAYS];
   __shared__ int wsum[2][NW];
+  __shared__ int hist[MAXM];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float full = nth - S.lite_margin;
+  if (adapt) {
+    if (tid < MAXM) hist[tid] = 0;
+    __syncthreads();
+  }
   // Each wave scans its RPW rays one at a time, lane j on sample j (coalesced flag / value
   // loads — all RPW rays' in flight at once — and ballots): refined = the flagged samples in
   // front of the first unflagged sample that is certainly full, or up to and including it when
@@ -903,7 +924,7 @@ __global__ __launch_bounds__(REFINE_SCAN_THREADS) void k_refine_scan(const Rende
       const bool in = rr < d.n_rays && lane < M;
       const size_t e = d.cand_off + (size_t)rr * M + lane;
       fv[u] = in ? refine[e] : 0;
-      yv[u] = (in && dense) ? dense[e] : __builtin_nanf("");
+      yv[u] = in ? dense[e] : __builtin_nanf("");
     }
 #pragma unroll
     for (int u = 0; u < RPW; ++u) {
@@ -912,7 +933,7 @@ __global__ __launch_bounds__(REFINE_SCAN_THREADS) void k_refine_scan(const Rende
       const uint64_t ub = __ballot((fv[u] == 0 || fv[u] == 3) && yv[u] <= full);
       const uint64_t tb = __ballot(fv[u] == 3), ab = __ballot(fv[u] >= 2);
       uint64_t b = fb;
-      if (ub) {
+      if (ub && !all) {
         const int stop = __builtin_ctzll(ub);
         b = fb & (((1ull << stop) - 1) | (tb & (1ull << stop)));
       }
@@ -923,6 +944,11 @@ __global__ __launch_bounds__(REFINE_SCAN_THREADS) void k_refine_scan(const Rende
       if (lane == u) {
         rbits[RPW * wv + u] = b;
         abits[RPW * wv + u] = b & ab;
+      }
+      if (adapt) {
+        const uint64_t ib = __ballot(yv[u] == yv[u]);           // in the ball and decoded
+        const int rank = ub ? __popcll(ib & ((1ull << __builtin_ctzll(ub)) - 1)) : M - 1;
+        if (lane == u && rr < d.n_rays) atomicAdd(&hist[min(rank, M - 1)], 1);
       }
     }
   }
@@ -950,6 +976,10 @@ __global__ __launch_bounds__(REFINE_SCAN_THREADS) void k_refine_scan(const Rende
     for (int k = 0; k < NW; ++k) { t += wsum[0][k]; a += wsum[1][k]; }
     ccnt[blockIdx.x] = t;
     if (a) atomicAdd(&S.n_audit, a);           // one atomic per chunk
+  }
+  if (adapt && tid < M) {                      // (hist complete: the barriers above)
+    const int h = hist[tid];
+    if (h) atomicAdd(&S.hist[tid], h);
   }
 }
 
@@ -2082,6 +2112,73 @@ __global__ void k_views_pose(const int2* __restrict__ tie, ObjState* st, const f
     mm4(st[t.x].T, cview + (size_t)(t.x + m) * 16, st[t.x + m].T);
 }
 
+// choose_windows: the object's render-pass windows for its next iteration, from this
+// iteration's termination ranks (ObjState.hist, k_refine_scan) — by one wave, lane j = rank j.
+// A ray whose first certainly-full sample has in-ball rank t, in window [a, b), is decoded up to
+// rank b - 1: b - 1 - t samples more than the result needs.  The rule: count every terminated
+// ray at its rank and, because ranks move by a sample or two between iterations and a late ray
+// falls into the wide last window, at ranks t - 1, t + 1 and t + 2 as well; take the P windows
+// 0 = w[0] < w[1] < ... < w[P] = M with w[1] >= the current first window (the first pass still
+// fills the chip) that minimise the summed over-decode of those counts.  An exact dynamic
+// programme over (windows, last boundary) in integers, ties to the smaller boundary: the same
+// counts give the same table, whatever order the atomics ran in.  Rays that never terminate cost
+// nothing under any schedule; an object with no terminated ray keeps the table it has.
+__device__ __forceinline__ void choose_windows(ObjState& S, const int M, const int P, const int lane) {
+  constexpr int INF = 0x3fffffff;
+  const int h0 = lane < M - 1 ? S.hist[lane] : 0;          // (bin M - 1: free under any schedule)
+  int hs = h0 + __shfl(h0, min(lane + 1, 63));
+  if (lane >= 1) hs += __shfl(h0, lane - 1);
+  if (lane >= 2) hs += __shfl(h0, lane - 2);
+  if (lane >= M) hs = 0;
+  // C[j], W[j]: counts and rank-weighted counts of ranks < j; cost of window [i, j):
+  // (j - 1)(C[j] - C[i]) - (W[j] - W[i])
+  const int ci = wave_incl_scan(hs, lane), wi = wave_incl_scan(hs * lane, lane);
+  const int C = ci - hs, W = wi - hs * lane;
+  const int Ct = __builtin_amdgcn_readlane(ci, 63), Wt = __builtin_amdgcn_readlane(wi, 63);
+  if (Ct == 0 || Ct > (1 << 22)) return;                  // no history (or counts past int range)
+  const int b1 = S.win[1];
+  int f = (lane >= b1 && lane < M) ? (lane - 1) * C - W : INF;   // one window [0, j)
+  int arg[WIN_MAX];
+#pragma unroll
+  for (int p = 2; p < WIN_MAX - 1; ++p) {                  // p windows end at boundary j = lane
+    arg[p] = 0;
+    if (p >= P) continue;
+    int best = INF;
+    for (int i = 1; i < M - 1; ++i) {
+      const int fi = __builtin_amdgcn_readlane(f, i);
+      const int v = fi + (lane - 1) * (C - __builtin_amdgcn_readlane(C, i)) - (W - __builtin_amdgcn_readlane(W, i));
+      if (i < lane && lane < M && fi < INF && v < best) {
+        best = v;
+        arg[p] = i;
+      }
+    }
+    f = best;
+  }
+  int w[WIN_MAX];                                          // the last window [i, M), then back
+  int best = INF, bi = 0;
+  for (int i = 1; i < M; ++i) {
+    const int fi = __builtin_amdgcn_readlane(f, i);
+    const int v = fi + (M - 1) * (Ct - __builtin_amdgcn_readlane(C, i)) - (Wt - __builtin_amdgcn_readlane(W, i));
+    if (fi < INF && v < best) {
+      best = v;
+      bi = i;
+    }
+  }
+  if (best >= INF) return;                                 // (cannot be: the current table is feasible)
+#pragma unroll
+  for (int p = WIN_MAX - 2; p >= 1; --p) {
+    w[p] = 0;
+    if (p > P - 1) continue;
+    w[p] = bi;
+    if (p >= 2) bi = __builtin_amdgcn_readlane(arg[p], bi);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int p = 1; p < WIN_MAX - 1; ++p)
+      if (p <= P - 1) S.win[p] = (unsigned char)w[p];
+  }
+}
+
 // solve_object: optimizer.py:131-194 for one object by one workgroup — the body of k_solve
 // (TIED = false: object o alone, nm = 1) and of k_solve_views (TIED = true: the object's nm views
 // are members o .. o + nm - 1, o the leader; their normal-equation sums are pooled, the one
@@ -2611,6 +2708,10 @@ __device__ __forceinline__ void solve_object(const int o, const int nm, const Ob
       for (int i = 0; i < CODE; ++i) tv[2 * NPAR + 19 + i] = z[i];
     }
   }
+  // the next iteration's render-pass windows, by the last wave while lane 0 updates the pose
+  // (an iteration discarded for an audit violation returned above: its object keeps its table)
+  if (P.n_win && tid >= SOLVE_THREADS - 64)
+    for (int m = 0; m < nm; ++m) choose_windows(st[o + m], P.M, P.n_win, tid & 63);
   if (trace_i && tid == 0) {
     int c[4] = {S.n_valid, S.k, S.n_eval, S.n_refine};
     if constexpr (TIED)               // the views' counts summed

@@ -310,6 +310,7 @@ SIGNATURES = {
     "dsr_batch_download": (C.c_int, [C.c_void_p, C.POINTER(ObjectOut)]),
     "dsr_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "dsr_batch_lite_diag": (C.c_int, [C.c_void_p, IP, C.c_int]),
+    "dsr_batch_windows": (C.c_int, [C.c_void_p, IP, IP, IP]),
     "dsr_batch_destroy": (C.c_int, [C.c_void_p]),
     "dsr_batch_create_capacity": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimParams), C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -309,6 +309,13 @@ int dsr_batch_stats(dsr_batch* b, dsr_stats* st);
  * HW_ID, XCC_ID, and how many polls took how many 100 MHz ticks before it expired
  * (csrc/dsr_dev.hpp: STD_*; 16 ints). */
 int dsr_batch_lite_diag(dsr_batch* b, int* rec, int n);
+/* Render-pass windows of the early ray termination (no reference counterpart): *adaptive = 1 if
+ * every object re-chooses its windows each iteration from where its rays terminated in the one
+ * before (the default for lite-pass batches on their default multi-pass schedule; results do not
+ * depend on the windows), 0 for the batch's fixed schedule; *n_bounds = passes + 1.  bounds, when
+ * not NULL, receives [n_obj][*n_bounds] in-ball-rank boundaries (0 ... M) as the last run left
+ * them (the batch must have run). */
+int dsr_batch_windows(dsr_batch* b, int* adaptive, int* n_bounds, int* bounds);
 int dsr_batch_destroy(dsr_batch* b);
 
 /* Fixed-capacity batches for a keyframe stream (BASELINE config 5; the per-keyframe loop
